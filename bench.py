@@ -11,7 +11,7 @@ path shards by packet with no data-path collective ("scaling": "weak"); ranks
 meet only at the barriers around the timed region and in the max-over-ranks
 time reduction.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--config c2|c3|c4|c5|slots|zslots|rx|zrx] [--len L] [--kind ip|payload]
                     [--headers] [--fused] [--batches K] [--rotate-bytes B]
                     [--cpu-seconds S] [--no-cpu-baseline] [--no-c5] [--no-extra]
@@ -22,7 +22,13 @@ is run as K = ceil(1 GiB / batch) distinct batches, each with its own seed,
 step i checksumming batch i mod K, so no step re-reads bytes the cache still
 holds; every packet of every batch is checked.  C2's 1.54 GB batch is K = 1.
 
-Every default line also carries (after the headline's timed region):
+A plain run does only what the headline figure needs: it sets the workload
+up, warms up, times the K steps and prints the line ("parity", "cpu_baseline"
+and "c5" are null).  --dump-outputs DIR then also writes what the last timed
+step computed (dump_outputs).  Everything else rides behind --full: the
+bit-exact check of every packet against the oracle ("parity"), the CPU
+baseline, the single-buffer figure of a rotating run (frac_l3_resident), the
+results all-gather of an N-rank run, and (after the headline's timed region):
 * "c5": SURVEY C5, the north star's strong-scaling curve -- 2^28 x 1472 B in
   total, split evenly over the N ranks, each rank's share checksummed as
   launches over a resident 2^25-packet (49 GB) window -- timed with its own
@@ -33,7 +39,9 @@ Every default line also carries (after the headline's timed region):
 * "c4": BASELINE configs[3], 2^24 Zipf(1) 64-1472 B packets packed, every
   packet checked;
 * roofline.frac_rotating: C2 over 4 rotating 1.54 GB batches.
---no-extra skips c3 / c4 / frac_rotating, --no-c5 the C5 leg.
+* "e2e": the host-memory calls end to end (e2e_leg).
+With --full, --no-extra skips c3 / c4 / frac_rotating, --no-c5 the C5 leg,
+--no-e2e the end-to-end object and --no-cpu-baseline the CPU baseline.
 --fused runs the fused IPv4 header + payload_cksum pass (wc_cksum_ip_udp_*).
 --config rx is the RX verdict pass (wc_rx_verdict_ragged) over a netmap RX
 ring of well-formed UDP frames (2048-B slots, valid IPv4 / IPv6 checksums).
@@ -67,6 +75,8 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip tabl
 GIB = float(1 << 30)
 C3_SIZES = (64, 256, 576, 1472, 9000)  # BASELINE configs[2]
 BATCH_SEED_STEP = 0x9E3779B9  # seed of batch k = rank seed + k * this
+DUMP_MAX_BYTES = 48 << 20  # all files of one --dump-outputs together
+DUMP_SEED = 0xD0C5  # of the sample a larger output is written as
 
 
 def parse(argv=None):
@@ -74,6 +84,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the parity check against "
+                         "the oracle, the CPU baseline, the c3 / c4 / ring / C5 / e2e legs "
+                         "(each still has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (float32; rank 0's batch)")
     ap.add_argument("--config", default="c2",
                     choices=["c2", "c3", "c4", "c5", "slots", "zslots", "rx", "zrx"])
     ap.add_argument("--len", type=int, default=1472, help="packet bytes for c3")
@@ -636,6 +653,29 @@ def parity_check(args, W):
     return {"checked_packets": checked, "mismatches": bad, **extra}
 
 
+def dump_outputs(args, W, steps, directory):
+    """--dump-outputs: the arrays a caller of the timed path receives, as the
+    last of the `steps` timed steps left them (the batch that step ran on),
+    one float32 DIR/<name>.npy each: "checksums" (or "verdicts" for the RX
+    rings) and, for the fused pass, "header_checksums".  The workload's bytes
+    are seeded, so the same arguments give the same files on every run and
+    build.  An array that would take the files past DUMP_MAX_BYTES in all is
+    written as a fixed sample: its elements at the sorted indices
+    default_rng(DUMP_SEED).integers(0, size, cap).  (The RX drop counter is
+    left out: it accumulates over the warm-up, whose length is timed.)"""
+    b = W.batches[(steps - 1) % len(W.batches)]
+    arrays = {"verdicts" if args.config in ("rx", "zrx") else "checksums": b["out"]}
+    if b.get("out_hdr") is not None:
+        arrays["header_checksums"] = b["out_hdr"]
+    cap = DUMP_MAX_BYTES // 4 // len(arrays)
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, cap))]
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float32))
+
+
 def c5_leg(args, dev, rank, world, coll_dev):
     """SURVEY C5 beside the headline (the north star's 1/2/4/8-GPU curve):
     2^28 x 1472 B in total, split evenly over the ranks (wc_shard_range's
@@ -1008,6 +1048,8 @@ def main():
     wc.gpu_init(local)
     if args.fused:  # the fused pass is payload_cksum over real UDP headers
         args.kind, args.headers = "payload", True
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_extra = args.no_c5 = args.no_e2e = True
 
     W = make_workload(args, dev, rank, world)
     n, nbytes, meta = W.n, W.nbytes, W.meta
@@ -1060,10 +1102,14 @@ def main():
     achieved = nbytes / (kernel_ms_max * 1e-3) / 1e9
     frac_job = value * GIB / 1e9 / (world * HBM_PEAK_GBPS)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, W, steps, args.dump_outputs)
+
+    # Everything below is beside the headline: a plain run skips it (--full).
     # Single-buffer figure beside a rotating run (the Infinity-Cache-resident
     # rate the rotation avoids).
     frac_l3 = None
-    if K > 1:
+    if K > 1 and args.full:
         one = SimpleNamespace(**vars(W))
         one.batches = W.batches[:1]
         T1 = Timer(one, dev, use_graph, rotate=1)
@@ -1073,17 +1119,20 @@ def main():
         frac_l3 = round(nbytes / (ms1 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
         del T1, one
 
-    parity = parity_check(args, W)
-    for key in list(parity):
-        if isinstance(parity[key], int):
-            parity[key] = wdist.sum_over_ranks(parity[key], coll_dev)
+    parity = None
+    if args.full:
+        parity = parity_check(args, W)
+        for key in list(parity):
+            if isinstance(parity[key], int):
+                parity[key] = wdist.sum_over_ranks(parity[key], coll_dev)
 
     # after the timed region the ranks exchange their 2-byte
     # results (RCCL all-gather over xGMI; host tensors for the gloo
     # rehearsal), so every rank holds the whole job's results in packet order.
     out = W.batches[0]["out"]
     gather = None
-    if (world > 1 or wdist._pg_active()) and out.numel() == n and out.element_size() == 2:
+    if (args.full and (world > 1 or wdist._pg_active()) and out.numel() == n
+            and out.element_size() == 2):
         src = out.view(torch.int16)
         if coll_dev.type != "cuda":
             src = src.cpu()

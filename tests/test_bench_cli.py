@@ -78,6 +78,66 @@ def test_rotation_covers_the_infinity_cache(batch, want):
     assert bench.rotation(batch, bench.parse(["--batches", "4"])) == 4
 
 
+def test_plain_run_is_the_default():
+    """Everything beside the headline rides behind --full, off by default."""
+    assert not bench.parse([]).full and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--full"]).full
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    assert bench.parse(["--steps", "7"]).steps == 7
+
+
+def _fake_workload(n, fused=False, batches=1):
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    bs = []
+    for k in range(batches):
+        out = torch.from_numpy(((np.arange(n, dtype=np.int64) * 40503 + k) & 0xFFFF)
+                               .astype(np.uint16))
+        bs.append({"buf": None, "out": out,
+                   "out_hdr": torch.from_numpy((out.numpy() ^ 0xFFFF).astype(np.uint16))
+                   if fused else None})
+    return SimpleNamespace(batches=bs)
+
+
+def test_dump_outputs_writes_the_last_steps_batch(tmp_path):
+    """float32 files of the batch the last timed step ran on (step i runs on
+    batch i mod K); the fused pass has two arrays."""
+    import numpy as np
+    W = _fake_workload(1000, fused=True, batches=3)
+    a = bench.parse(["--fused"])
+    bench.dump_outputs(a, W, 5, tmp_path / "d")  # steps 0..4: the last on batch 4 % 3 = 1
+    got = np.load(tmp_path / "d" / "checksums.npy")
+    hdr = np.load(tmp_path / "d" / "header_checksums.npy")
+    assert got.dtype == np.float32 and hdr.dtype == np.float32
+    want = W.batches[1]["out"].numpy()
+    assert np.array_equal(got, want.astype(np.float32))
+    assert np.array_equal(hdr, (want ^ 0xFFFF).astype(np.float32))
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["checksums.npy",
+                                                                 "header_checksums.npy"]
+    bench.dump_outputs(bench.parse(["--config", "rx"]), _fake_workload(10), 1, tmp_path / "r")
+    assert [p.name for p in (tmp_path / "r").iterdir()] == ["verdicts.npy"]
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """Past DUMP_MAX_BYTES in all, every array is a fixed seeded sample: the
+    same elements on every run, within the budget."""
+    import numpy as np
+    assert bench.DUMP_MAX_BYTES <= 64_000_000 - 4096  # .npy headers included
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 600)
+    W = _fake_workload(1000, fused=True)
+    a = bench.parse(["--fused"])
+    bench.dump_outputs(a, W, 1, tmp_path / "a")
+    bench.dump_outputs(a, W, 1, tmp_path / "b")
+    got = np.load(tmp_path / "a" / "checksums.npy")
+    assert got.size == 300 and got.dtype == np.float32
+    assert np.array_equal(got, np.load(tmp_path / "b" / "checksums.npy"))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 1000, 300))
+    assert np.array_equal(got, W.batches[0]["out"].numpy()[idx].astype(np.float32))
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= 4 * 600 + 2 * 256
+
+
 def test_default_line_carries_the_secondary_legs():
     a = bench.parse([])
     assert not a.no_extra and a.c3_packets == 1 << 20 and a.c4_packets == 1 << 24

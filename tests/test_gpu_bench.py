@@ -15,6 +15,8 @@ ROOT = Path(__file__).resolve().parent.parent
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
         "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
         "roofline", "cpu_baseline"}
+# the parity check, the CPU baseline and every leg beside the headline: --full
+BENCH = [sys.executable, str(ROOT / "bench.py"), "--full"]
 
 
 def _last_json(out: str) -> dict:
@@ -50,7 +52,7 @@ def test_bench_one_gpu_line(gpu):
     """The driver's line at reduced size: C2 headline, CPU baseline, the C5
     strong-scaling leg (2^22 packets over a 2^20 window here) and the c3 / c4
     objects and C2 rotating cross-check (rotating over >= 64 MiB here)."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "1",
+    r = subprocess.run([*BENCH, "--steps", "5", "--warmup", "1",
                         "--packets", "65536", "--cpu-seconds", "0.5", *SMALL_C5, *SMALL_EXTRA],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -87,11 +89,47 @@ def test_bench_one_gpu_line(gpu):
     check_e2e(line["e2e"], 1)
 
 
+def test_bench_plain_run_and_dump(gpu, tmp_path):
+    """A plain run (no --full) is the headline alone: the same line with
+    nothing measured or checked beside it, exactly --steps timed steps, and
+    --dump-outputs writes the last step's checksums -- compared here with
+    the oracle over the same seeded bytes."""
+    import numpy as np
+    import torch
+
+    import warpcore_amd as wc
+    from oracle import c_oracle
+    from warpcore_amd import synth
+
+    n, L = 65536, 1472
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "7",
+                        "--warmup", "1", "--packets", str(n), "--batches", "1",
+                        "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _last_json(r.stdout)
+    assert KEYS <= set(line)
+    assert line["steps"] == 7 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["roofline"]["timing"].startswith("hipGraph replay (7 launches per graph)")
+    assert 0 < line["roofline"]["frac"] < 1.5
+    assert line["parity"] is None and line["cpu_baseline"] is None and line["c5"] is None
+    assert not {"c3", "c4", "rings", "e2e", "results_allgather"} & set(line)
+    assert "rotating" not in line["roofline"]
+    got = np.load(tmp_path / "out" / "checksums.npy")
+    assert [p.name for p in (tmp_path / "out").iterdir()] == ["checksums.npy"]
+    assert got.dtype == np.float32 and got.shape == (n,)
+    d = torch.empty(n * L + 64, dtype=torch.uint8, device=gpu)
+    wc.synth_fill(d, synth.SEED, nbytes=n * L)
+    want = c_oracle.cksum_strided(d[: n * L].cpu().numpy(), L, L, n, kind=0)
+    assert np.array_equal(got, want.astype(np.float32))
+
+
 def test_bench_c3_rotating_line(gpu):
     """`--config c3` rotates over distinct batches (HBM, not the Infinity
     Cache), replays its launches from a hipGraph, checks every batch and
     reports the single-buffer rate beside it."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", "c3", "--len", "64",
+    r = subprocess.run([*BENCH, "--config", "c3", "--len", "64",
                         "--steps", "20", "--warmup", "2", "--packets", "65536",
                         "--rotate-bytes", str(16 << 20), "--no-c5", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
@@ -111,7 +149,7 @@ def test_bench_two_ranks_rehearsal(gpu):
     env = dict(os.environ, WC_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2",
+                        "--master-port", str(port), str(ROOT / "bench.py"), "--full", "--gpus", "2",
                         "--steps", "5", "--warmup", "1", "--packets", "65536",
                         "--cpu-seconds", "0.3", *SMALL_C5, *SMALL_EXTRA],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
@@ -144,7 +182,7 @@ def test_bench_eight_ranks_rehearsal(gpu):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["WC_DIST_BACKEND"] = "gloo"
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8",
+    r = subprocess.run([*BENCH, "--gpus", "8",
                         "--steps", "5", "--warmup", "1", "--packets", "65536",
                         "--cpu-seconds", "0.3", *SMALL_C5, *SMALL_EXTRA],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -184,7 +222,7 @@ def test_bench_eight_ranks_rehearsal(gpu):
 def test_bench_other_configs(gpu, args):
     """The secondary bench lines (C4, payload_cksum, the netmap RX-ring layout)
     stay runnable and bit-exact."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([*BENCH, "--steps", "3", "--warmup", "1",
                         "--cpu-seconds", "0.2", "--no-c5", "--no-extra", *args],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -201,7 +239,7 @@ def test_bench_spawns_ranks_without_torchrun(gpu):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["WC_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2",
+    r = subprocess.run([*BENCH, "--gpus", "2",
                         "--steps", "5", "--warmup", "1", "--packets", "65536", "--no-c5",
                         "--no-cpu-baseline", "--no-extra", "--batches", "1"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
@@ -216,7 +254,7 @@ def test_bench_spawns_ranks_without_torchrun(gpu):
 def test_bench_c5_windowed(gpu):
     """SURVEY C5's 1-GPU shape at reduced size: 2^22 x 1472 B as 4 launches
     over a resident 2^20-packet window, the last window checked in full."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--config", "c5",
+    r = subprocess.run([*BENCH, "--config", "c5",
                         "--total-packets", str(1 << 22), "--window-packets", str(1 << 20),
                         "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
@@ -236,7 +274,7 @@ def test_bench_c5_two_rank_split(gpu):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["WC_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--config", "c5",
+    r = subprocess.run([*BENCH, "--gpus", "2", "--config", "c5",
                         "--total-packets", str(1 << 22), "--window-packets", str(1 << 20),
                         "--steps", "3", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
@@ -258,7 +296,7 @@ def test_bench_rccl_code_path_one_rank(gpu):
     s.close()
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(port), WC_DIST_FORCE_PG="1", WC_DIST_BACKEND="nccl")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5",
+    r = subprocess.run([*BENCH, "--gpus", "1", "--steps", "5",
                         "--warmup", "1", "--packets", "65536", "--no-cpu-baseline",
                         "--no-extra", *SMALL_C5],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)

@@ -8,7 +8,7 @@ export WC_NO_BUILD=1 TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-e2e_order}
 mkdir -p "$OUT"
 for i in 1 2; do
-    timeout -k 10 200 python bench.py --no-c5 --no-extra --no-rings --no-cpu-baseline \
+    timeout -k 10 200 python bench.py --full --no-c5 --no-extra --no-rings --no-cpu-baseline \
         > "$OUT/e2e_only_$i.json" 2> "$OUT/e2e_only_$i.err" || exit 1
     python - "$OUT/e2e_only_$i.json" <<'PY'
 import json, sys

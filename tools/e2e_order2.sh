@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG:-e2e_order2}
 mkdir -p "$OUT"
 run() {  # $1 = name, rest = bench flags
     local name=$1; shift
-    timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || exit 1
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || exit 1
     python - "$OUT/$name.json" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

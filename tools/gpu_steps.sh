@@ -9,8 +9,8 @@
 # call -- nothing else touches the GPU after it.
 #   pytest        the whole -m gpu suite (PYTEST_ARGS adds options / a -k filter)
 #   smoke         __graft_entry__.smoke()
-#   bench         the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
-#   bench_args    bench.py $BENCH_ARGS (> bench_args.json)
+#   bench         the whole bench line: bench.py --gpus 1 --steps 20 --warmup 5 --full
+#   bench_args    bench.py $BENCH_ARGS (> bench_args.json; --full for more than the headline)
 #   prof_c2       rocprofv3 --kernel-trace --stats of the driver's headline command
 #   diag_headline tools/diag_headline.py (the headline's whole-job gap, by issue mode)
 #   tune          tools/tune.py once per '|'-separated argument set in $TUNE_ARGS
@@ -51,7 +51,7 @@ for s in ${STEPS:-pytest smoke bench}; do
         smoke)
             step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
         bench)
-            step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5
+            step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full
             grep '^{' "$OUT/bench.log" > "$OUT/bench.json" ;;
         bench_args)
             step bench_args 600 python bench.py ${BENCH_ARGS:-}

@@ -9,7 +9,7 @@ OUT=gpurun_out/${TAG:-rings_count}
 mkdir -p "$OUT"
 for rep in $(seq 1 "${REPS:-4}"); do
     for lib in ${LIBS}; do
-        WC_LIB="$lib" timeout -k 10 200 python bench.py ${BENCH_FLAGS:---no-c5 --no-e2e --no-cpu-baseline} \
+        WC_LIB="$lib" timeout -k 10 200 python bench.py --full ${BENCH_FLAGS:---no-c5 --no-e2e --no-cpu-baseline} \
             > "$OUT/r$rep.json" 2> "$OUT/r$rep.err" || exit 1
         python - "$OUT/r$rep.json" "$(basename "$lib")" "$rep" <<'PY'
 import json, sys

@@ -34,7 +34,8 @@ for c in ${CFGS:-c2 c4 c4pl slotspl}; do
         *) echo "unknown config $c"; exit 2 ;;
     esac
     echo "== $c: bench"
-    c5=""; [ "$c" = c2 ] || c5="--no-c5"   # the C5 leg rides on the headline line
+    # every leg of the line (--full); the C5 leg rides on the headline line alone
+    c5="--full"; [ "$c" = c2 ] || c5="--full --no-c5"
     timeout -k 10 300 python bench.py $a $c5 > gpurun_out/round/bench_${TAG}_$c.json \
         2> gpurun_out/round/bench_${TAG}_$c.err || { tail gpurun_out/round/bench_${TAG}_$c.err; exit 1; }
     cat gpurun_out/round/bench_${TAG}_$c.json
