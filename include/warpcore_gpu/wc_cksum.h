@@ -130,6 +130,57 @@ int wc_rx_verdict_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
                        const uint16_t *h_frame_len, uint64_t n, uint8_t *h_verdict,
                        uint64_t *h_drops);
 
+/* --- TX seal: both checksums computed and stored in the frames ----------- */
+
+/* What mk_ip4_hdr and udp_tx do to a frame (ip4.c:184-186, udp.c:209-213),
+ * for a batch of Ethernet frames: the device parses each frame, computes
+ * ip_cksum(ip, hl) with header bytes 10..11 taken as 0 (IPv4; options
+ * included) and payload_cksum(ip, hl + udp_len) with udp->cksum taken as 0,
+ * and stores both raw (native uint16, any address parity) into the frame.
+ * Whatever the two fields hold on entry does not matter, so the call is
+ * idempotent; a computed UDP checksum of 0 is stored as 0 (udp.c:213).  The
+ * checks run in the order of the RX chain above; the first that fails names
+ * the code.  A sealed frame is one wc_rx_verdict_* accepts. */
+enum wc_tx_status {
+    WC_TX_SEALED = 0,          /* UDP over IPv4 / IPv6: every checksum field the frame has is written */
+    WC_TX_SEALED_ZERO_UDP = 1, /* WC_TX_ZERO_UDP_CKSUM: IPv4 header checksum written, udp->cksum written 0 */
+    WC_TX_IP_ONLY = 2,         /* IPv4, not UDP or a fragment (offset != 0): header checksum written, nothing else */
+    WC_TX_NOT_UDP = 3,         /* IPv6, another next header: untouched (ICMPv6 is the host's, icmp6.c:73) */
+    WC_TX_NOT_IP = 4,          /* EtherType neither IPv4 nor IPv6 (ARP): untouched */
+    WC_TX_BAD_VERSION = 5,     /* version nibble != the EtherType's: untouched */
+    WC_TX_MALFORMED = 6,       /* IHL < 5, IP payload < 8, or MIN(udp->len, ip_plen) < 8: untouched */
+    WC_TX_TRUNCATED = 7,       /* a byte that would be read or written lies past the frame: untouched */
+};
+#define WC_TX_IS_ERROR(s) ((s) >= WC_TX_BAD_VERSION)
+
+#define WC_TX_ZERO_UDP_CKSUM 1u /* the socket's enable_udp_zero_checksums (udp.c:212): no payload byte is read */
+#define WC_TX_NO_STORE 2u       /* compute only: frames untouched, both d_out arrays required */
+
+/* Frame i is the Ethernet frame [d_base + d_off[i], + d_frame_len[i]); the
+ * frames of one call must not overlap (they may share 16-byte chunks and
+ * cache lines).  d_status[i] receives its enum wc_tx_status code (uint8);
+ * d_out_ip_hdr / d_out_udp (optional) the two values, 0 where none is
+ * computed; *d_errors (device uint64, optional, accumulated) counts the
+ * WC_TX_IS_ERROR frames.  "Untouched" means no byte of the frame is written;
+ * for every status no byte outside the frame is read or written, and no byte
+ * of the frame but the two fields is ever written.  Unknown flag bits, and
+ * WC_TX_NO_STORE without both out arrays, are WC_EINVAL.  One asynchronous
+ * launch on `stream`. */
+int wc_tx_seal_ragged(void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
+                      uint64_t n, uint32_t flags, uint8_t *d_status,
+                      uint16_t *d_out_ip_hdr, uint16_t *d_out_udp,
+                      uint64_t *d_errors, void *stream);
+
+/* Host-memory frames (a w_iov_sq's buffers in w->mem, ideally registered with
+ * wc_host_register), every frame inside [h_base, h_base + h_bytes) (WC_EINVAL
+ * otherwise): the device computes over the host paths of wc_cksum_host (a
+ * zero-copy launch, in-place streaming or the pipeline; never the resident
+ * server) and the calling thread makes the stores.  Synchronous; *h_errors
+ * (optional) = the WC_TX_IS_ERROR count.  WC_TX_NO_STORE is WC_EINVAL here. */
+int wc_tx_seal_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off,
+                    const uint16_t *h_frame_len, uint64_t n, uint32_t flags,
+                    uint8_t *h_status, uint64_t *h_errors);
+
 /* --- host-memory batch (end-to-end: pinned H2D, kernel, D2H) ------------- */
 
 /* Same as wc_cksum_ragged, but every buffer is host memory: packet i is

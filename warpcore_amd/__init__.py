@@ -15,7 +15,10 @@ from .cksum import (KIND_IP, KIND_PAYLOAD, SclkProbe, WcError, cksum_host, cksum
                     verify_ragged, verify_strided, version, shard_devices,
                     rx_verdict_ragged, rx_verdict_host, RX_NAMES, RX_DROPS,
                     RX_OK, RX_OK_NO_CKSUM, RX_BAD_IP_CKSUM, RX_BAD_UDP_CKSUM, RX_SHORT,
-                    RX_FRAGMENT, RX_BAD_VERSION, RX_NOT_UDP, RX_NOT_IP, RX_TRUNCATED)
+                    RX_FRAGMENT, RX_BAD_VERSION, RX_NOT_UDP, RX_NOT_IP, RX_TRUNCATED,
+                    tx_seal_ragged, tx_seal_host, TX_NAMES, TX_ERRORS,
+                    TX_SEALED, TX_SEALED_ZERO_UDP, TX_IP_ONLY, TX_NOT_UDP, TX_NOT_IP,
+                    TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED)
 
 __all__ = [
     "KIND_IP", "KIND_PAYLOAD", "SclkProbe", "WcError", "cksum_host", "cksum_host_multi",
@@ -28,4 +31,7 @@ __all__ = [
     "verify_strided", "version", "shard_devices", "rx_verdict_ragged", "rx_verdict_host",
     "RX_NAMES", "RX_DROPS", "RX_OK", "RX_OK_NO_CKSUM", "RX_BAD_IP_CKSUM", "RX_BAD_UDP_CKSUM",
     "RX_SHORT", "RX_FRAGMENT", "RX_BAD_VERSION", "RX_NOT_UDP", "RX_NOT_IP", "RX_TRUNCATED",
+    "tx_seal_ragged", "tx_seal_host", "TX_NAMES", "TX_ERRORS", "TX_SEALED",
+    "TX_SEALED_ZERO_UDP", "TX_IP_ONLY", "TX_NOT_UDP", "TX_NOT_IP", "TX_BAD_VERSION",
+    "TX_MALFORMED", "TX_TRUNCATED",
 ]

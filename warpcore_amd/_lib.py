@@ -23,6 +23,7 @@ _lib = None
 
 # Every symbol the public header declares, with its ctypes signature.
 _u16, _u64, _int, _vp = ctypes.c_uint16, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p
+_u32 = ctypes.c_uint32
 SIGNATURES = {
     "ip_cksum": (_u16, [_vp, _u16]),
     "payload_cksum": (_u16, [_vp, _u16]),
@@ -34,6 +35,8 @@ SIGNATURES = {
     "wc_cksum_ip_udp_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "wc_rx_verdict_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "wc_rx_verdict_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "wc_cksum_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _int]),
     "wc_cksum_ip_udp_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "wc_server_stats": (_int, [ctypes.POINTER(_u64), ctypes.POINTER(_u64),

@@ -370,6 +370,69 @@ def rx_verdict_host(buf: np.ndarray, offsets: np.ndarray,
 
 
 # --------------------------------------------------------------------------
+# TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
+
+# enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)
+TX_SEALED, TX_SEALED_ZERO_UDP, TX_IP_ONLY, TX_NOT_UDP, TX_NOT_IP, TX_BAD_VERSION, \
+    TX_MALFORMED, TX_TRUNCATED = range(8)
+TX_NAMES = ("sealed", "sealed_zero_udp", "ip_only", "not_udp", "not_ip", "bad_version",
+            "malformed", "truncated")
+TX_ERRORS = (TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED)
+_TX_ZERO_UDP_CKSUM, _TX_NO_STORE = 1, 2
+
+
+def tx_seal_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                   zero_udp: bool = False, store: bool = True, stream=None,
+                   check: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                torch.Tensor]:
+    """Seal every Ethernet frame ``base[off[i] : off[i] + frame_len[i]]`` in
+    place (wc_tx_seal_ragged): the IPv4 header checksum and the UDP checksum,
+    each computed with its field taken as 0 and stored raw into the frame
+    (``zero_udp``: udp->cksum = 0, the zero-checksum socket; ``store=False``:
+    compute only, ``base`` untouched).  The frames must not overlap.  Returns
+    (uint8 status ``TX_*`` per frame, uint16 header checksums, uint16 UDP
+    checksums -- 0 where none is computed --, int64 count of ``TX_ERRORS``
+    frames)."""
+    _same_device(base, offsets=offsets, lengths=frame_lens)
+    n = _check_ragged_shapes(offsets, frame_lens)
+    if not base.is_contiguous():
+        raise ValueError("base must be contiguous")
+    if base.element_size() != 1:
+        raise ValueError("base must be a 1-byte tensor (the frames are written in place)")
+    if check and n:
+        _ragged_bounds(_nbytes(base), offsets, frame_lens, KIND_IP)
+    status = torch.empty(n, dtype=torch.uint8, device=base.device)
+    hdr = torch.empty(n, dtype=torch.uint16, device=base.device)
+    udp = torch.empty(n, dtype=torch.uint16, device=base.device)
+    errors = torch.zeros(1, dtype=torch.int64, device=base.device)
+    flags = (_TX_ZERO_UDP_CKSUM if zero_udp else 0) | (0 if store else _TX_NO_STORE)
+    with _on_device(base.device):
+        _check("wc_tx_seal_ragged", _lib.active().wc_tx_seal_ragged(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, flags,
+            status.data_ptr(), hdr.data_ptr(), udp.data_ptr(), errors.data_ptr(),
+            _stream_ptr(stream, base.device)))
+    return status, hdr, udp, errors
+
+
+def tx_seal_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray,
+                 zero_udp: bool = False) -> Tuple[np.ndarray, int]:
+    """tx_seal_ragged over host memory (wc_tx_seal_host, synchronous): the
+    frames in ``buf`` are sealed in place; (uint8 status codes, error count)."""
+    if not isinstance(buf, np.ndarray) or not buf.flags["C_CONTIGUOUS"] \
+            or not buf.flags["WRITEABLE"] or buf.dtype.itemsize != 1:
+        raise ValueError("tx_seal_host writes the frames in place: buf must be a writable "
+                         "C-contiguous 1-byte numpy array")
+    flat = buf.reshape(-1).view(np.uint8)
+    _, off, lens = _host_batch_args(flat, offsets, frame_lens)
+    status = np.empty(off.size, dtype=np.uint8)
+    errors = ctypes.c_uint64()
+    _check("wc_tx_seal_host", _lib.active().wc_tx_seal_host(
+        flat.ctypes.data, flat.size, off.ctypes.data, lens.ctypes.data, off.size,
+        _TX_ZERO_UDP_CKSUM if zero_udp else 0, status.ctypes.data, ctypes.byref(errors)))
+    return status, int(errors.value)
+
+
+# --------------------------------------------------------------------------
 # Host-memory batches (end-to-end path).
 
 def cksum_host(buf: np.ndarray, offsets: np.ndarray, lengths: np.ndarray,

@@ -179,6 +179,17 @@ hipError_t launch_rx_verdict(const void *base, const uint64_t *offs, const uint1
                              hipStream_t st, int mode = 0, uint32_t *tally = nullptr,
                              uint32_t gen = 0, int max_grid = 0);
 
+// TX seal of Ethernet frames [base + offs[i], + flens[i]) (wc_k_tx.hip): both
+// checksums computed with their fields taken as 0 and stored raw into the
+// frame, status[i] its enum wc_tx_status code; out_ip / out_udp (optional)
+// receive the values, 0 where none is computed; errors (optional) accumulates
+// the WC_TX_IS_ERROR frames.  flags: kTxZeroUdp (udp->cksum = 0, no payload
+// byte read) | kTxNoStore (compute only: no frame byte is written).
+constexpr uint32_t kTxZeroUdp = 1, kTxNoStore = 2;
+hipError_t launch_tx_seal(void *base, const uint64_t *offs, const uint16_t *flens, uint64_t n,
+                          uint32_t flags, uint8_t *status, uint16_t *out_ip, uint16_t *out_udp,
+                          uint64_t *errors, bool nt, hipStream_t st);
+
 // Resident small-batch server (wc_k_serve.hip).  Host-mapped pinned memory:
 // one record per packet, written by the host (seq last), polled / read by the
 // server's waves; one result slot per packet, written by the GPU in one

@@ -26,7 +26,7 @@
 // Every load stays inside its frame (chunks that overlap [frame, frame +
 // flen) only); whatever the reference would read past the frame is
 // WC_RX_TRUNCATED.  Roofline: HBM, the checked frames' bytes once.
-#include "wc_seg.h"
+#include "wc_rx_hdr.h"
 
 #ifdef WC_DIAG_STAMPS
 // Timing diagnostic build only (tools/rx_stamps.py): per tile, lane 0 stores
@@ -65,52 +65,6 @@ struct RxParse {
     uint32_t verdict; // final unless need
     bool need;        // the UDP checksum must be verified
 };
-
-// Two aligned chunks holding frame bytes from `at` on, each loaded only if it
-// overlaps the frame (else the zero chunk): never a page the frame does not
-// touch.
-struct Win2 {
-    u32x4 x, y;
-};
-
-__device__ __forceinline__ Win2 win2_load(uint64_t at, uint64_t fend, bool on, uint64_t zero)
-{
-    const uint64_t c = at & ~15ull;
-    Win2 w;
-    w.x = load_chunk<false>(on && c < fend ? c : zero);
-    w.y = load_chunk<false>(on && c + 16u < fend ? c + 16u : zero);
-    return w;
-}
-
-constexpr int kHdrChunks = 5; // an IPv4 header (<= 60 B) at any phase
-
-// The header view shared by both parses: EtherType, version, IHL, lengths.
-struct RxHdr {
-    bool v4, v6, version_ok, hdr_in, frag, udp_in;
-    uint32_t hl, room, proto, ip_plen;
-};
-
-__device__ __forceinline__ RxHdr rx_hdr(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t flen)
-{
-    RxHdr x;
-    const uint32_t etype = ((f0 & 0xFFu) << 8) | ((f0 >> 8) & 0xFFu); // eth.h:44-53
-    const uint32_t b0 = (f0 >> 16) & 0xFFu;                              // vhl / vfc
-    x.v4 = etype == 0x0800u;
-    x.v6 = etype == 0x86DDu;
-    x.room = flen >= 14u ? flen - 14u : 0u; // IP bytes inside the frame
-    x.hl = x.v4 ? (b0 & 15u) * 4u : 40u;    // ip4.h:88-92, udp.c:113
-    x.version_ok = (b0 >> 4) == (x.v4 ? 4u : 6u);
-    // Header fields (ip4.h:55-66, ip6.h:45-57): valid once the header is in.
-    x.hdr_in = (x.v4 || x.v6) && x.room >= 1u && x.version_ok &&
-               x.room >= (x.v4 ? max(x.hl, 20u) : 40u);
-    x.proto = x.v4 ? f2 >> 24 : f2 & 0xFFu; // p @9 / next_hdr @6
-    // IP4_OFFMASK 0xff1f on the native word @6: the fragment offset (ip4.h:49)
-    x.frag = x.v4 && (((f2 & 0x1Fu) | (f2 & 0xFF00u)) != 0u);
-    x.ip_plen = x.v4 ? ((((f1 & 0xFFu) << 8) | ((f1 >> 8) & 0xFFu)) - x.hl) & 0xFFFFu // udp.c:104
-                     : (((f1 >> 16) & 0xFFu) << 8) | (f1 >> 24);                     // udp.c:114
-    x.udp_in = x.hdr_in && x.proto == 17u && x.ip_plen >= 8u && x.room >= x.hl + 8u;
-    return x;
-}
 
 // The reference's decision chain (eth_rx -> ip4_rx / ip6_rx -> udp_rx); bytes
 // past the frame only feed decisions that the length checks have made.
@@ -159,24 +113,15 @@ __device__ __forceinline__ RxParse rx_decide(uint64_t fa, uint32_t flen, bool va
     return h;
 }
 
-// Steps 1 and 2 in ONE load round (rx_load, then rx_parse on what it
-// loaded): the frame's first five aligned chunks
+// Steps 1 and 2 in ONE load round (rx_load of wc_rx_hdr.h, then rx_parse on
+// what it loaded): the frame's first five aligned chunks
 // (frame bytes [0, 65) at least, each chunk loaded only if it overlaps the
 // frame) hold the Ethernet header, an IPv4 header of up to 40 bytes or the
 // IPv6 header, and the UDP length / checksum fields after either.  A lane
 // with a longer IPv4 header (options > 20 B) or a malformed IHL < 5 sets
 // `slow` and is re-parsed by rx_parse_slow.  Two dependent load rounds per tile cost the mixed-size ring
 // its headroom over payload_cksum alone.
-__device__ __forceinline__ void rx_load(uint64_t fa, uint32_t flen, bool valid, uint64_t zero,
-                                        u32x4 (&c)[5])
-{
-    const uint64_t fend = fa + flen;
-    const uint64_t cf = fa & ~15ull;
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        c[k] = load_chunk<false>(valid && cf + 16ull * k < fend ? cf + 16ull * k : zero);
-}
-
+//
 // The same five chunks, loaded transposed (HT): instruction i reads frames
 // 16 i .. 16 i + 15, four lanes per frame, lane 4 f' + j its chunk j -- 64
 // contiguous bytes per frame, one cache line instead of four separate

@@ -4,6 +4,7 @@
 //   wc_rt_config.cpp   configuration (the WC_* table), device state, lifetime
 //   wc_rt_plan.cpp     launch planner, device-resident batch calls, scalar drop-ins
 //   wc_rt_rx.cpp       RX verdict launches (ADAPT: EARLY or HT per launch)
+//   wc_rt_tx.cpp       TX seal: the device call, and the host call's stores
 //   wc_rt_server.cpp   host side of the resident small-batch server
 //   wc_rt_host.cpp     host-memory batches: zero-copy launch, staging, pipeline
 //   wc_rt_multi.cpp    the batch split over the GPUs of one node
@@ -39,6 +40,14 @@ constexpr int kFlatMinDefault = 0;                // ragged: flat kernel from n 
 // header's ip_cksum into a second array; wc_cksum_ip_udp_host).
 constexpr int kKindRx = 2;
 constexpr int kKindFused = 3;
+// The TX seal's compute pass (wc_tx_seal_host: the kernel in its no-store
+// mode, lengths = frame lengths): udp->cksum values into the main results,
+// the IPv4 header checksums into the second array, the 1-byte status codes
+// into a third; kKindTxZero is the zero-checksum socket's pass.  Never the
+// resident server's.
+constexpr int kKindTx = 4;
+constexpr int kKindTxZero = 5;
+inline bool kind_is_tx(int kind) { return kind == kKindTx || kind == kKindTxZero; }
 
 // Small batches over registered memory skip the copy engines: the kernel
 // reads the packets straight out of the page-locked region over PCIe, and
@@ -58,11 +67,13 @@ struct HostPipe {
     uint16_t *d_len[kPipe] = {};
     uint16_t *d_out[kPipe] = {};
     uint16_t *d_out2[kPipe] = {};  // fused pass: the IPv4 header checksums
+    uint8_t *d_st[kPipe] = {};     // TX seal pass: the status codes
     uint8_t *h_bytes[kPipe] = {};  // pinned staging for unregistered input
     uint64_t *h_off[kPipe] = {};   // pinned, rebased offsets
     uint16_t *h_len[kPipe] = {};
     uint16_t *h_out[kPipe] = {};
     uint16_t *h_out2[kPipe] = {};
+    uint8_t *h_st[kPipe] = {};
     bool ready = false;
 };
 
@@ -72,6 +83,7 @@ struct ZeroCopy {
     uint16_t *h_len = nullptr, *d_len = nullptr;
     uint16_t *h_out = nullptr, *d_out = nullptr;
     uint16_t *h_out2 = nullptr, *d_out2 = nullptr; // fused pass: header checksums
+    uint8_t *h_st = nullptr, *d_st = nullptr;      // TX seal pass: status codes
     bool ready = false;
 };
 
@@ -88,6 +100,7 @@ struct ZcStream {
     uint16_t *h_len[2] = {}, *d_len[2] = {};
     uint16_t *h_out[2] = {}, *d_out[2] = {};
     uint16_t *h_out2[2] = {}, *d_out2[2] = {}; // fused pass: header checksums
+    uint8_t *h_st[2] = {}, *d_st[2] = {};      // TX seal pass: status codes
     bool ready = false;
 };
 
@@ -329,7 +342,14 @@ uint64_t span_of(uint16_t len, int kind);
 int out_size(int kind);
 int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
                    const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                   uint16_t *h_out2 = nullptr);
+                   uint16_t *h_out2 = nullptr, uint8_t *h_st = nullptr);
+// A host-memory batch on the current device by the rules of wc_cksum_host
+// (server, zero-copy launch, zero-copy stream or pipeline).  h_out2: the
+// fused pair's and the TX seal pass's header checksums; h_st: the TX seal
+// pass's status codes.
+int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
+               const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
+               uint16_t *h_out2 = nullptr, uint8_t *h_st = nullptr);
 // Every packet of a host batch inside [0, h_bytes); whether the offsets
 // ascend, the bytes the packets' checks read, and (optional) the byte range
 // they span.
@@ -351,6 +371,7 @@ struct PipeRun {
     const uint16_t *h_len = nullptr;
     uint8_t *h_out = nullptr; // out_size(kind) bytes per packet
     uint16_t *h_out2 = nullptr; // fused pair: the header checksums
+    uint8_t *h_st = nullptr;    // TX seal pass: the status codes
     int kind = WC_CKSUM_IP;
     uint64_t i = 0, hi = 0;
     uint64_t pend_lo[kPipe] = {}, pend_n[kPipe] = {};

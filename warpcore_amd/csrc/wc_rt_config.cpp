@@ -255,6 +255,7 @@ int wc_gpu_fini(void)
             (void)hipHostFree(D.zc.h_len);
             (void)hipHostFree(D.zc.h_out);
             (void)hipHostFree(D.zc.h_out2);
+            (void)hipHostFree(D.zc.h_st);
         }
         zs_free(D.zs);
         if (D.srv.ready) {

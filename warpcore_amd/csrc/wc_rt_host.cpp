@@ -30,11 +30,13 @@ void pipe_free(HostPipe &P)
         (void)hipFree(P.d_len[s]);
         (void)hipFree(P.d_out[s]);
         (void)hipFree(P.d_out2[s]);
+        (void)hipFree(P.d_st[s]);
         (void)hipHostFree(P.h_bytes[s]);
         (void)hipHostFree(P.h_off[s]);
         (void)hipHostFree(P.h_len[s]);
         (void)hipHostFree(P.h_out[s]);
         (void)hipHostFree(P.h_out2[s]);
+        (void)hipHostFree(P.h_st[s]);
         if (P.done[s])
             (void)hipEventDestroy(P.done[s]);
         if (P.st[s])
@@ -57,11 +59,13 @@ int pipe_init_locked(HostPipe &P)
             hipMalloc((void **)&P.d_len[s], kChunkPkts * 2) != hipSuccess ||
             hipMalloc((void **)&P.d_out[s], kChunkPkts * 2) != hipSuccess ||
             hipMalloc((void **)&P.d_out2[s], kChunkPkts * 2) != hipSuccess ||
+            hipMalloc((void **)&P.d_st[s], kChunkPkts) != hipSuccess ||
             hipHostMalloc((void **)&P.h_bytes[s], kChunkBytes + 64, 0) != hipSuccess ||
             hipHostMalloc((void **)&P.h_off[s], kChunkPkts * 8, 0) != hipSuccess ||
             hipHostMalloc((void **)&P.h_len[s], kChunkPkts * 2, 0) != hipSuccess ||
             hipHostMalloc((void **)&P.h_out[s], kChunkPkts * 2, 0) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_out2[s], kChunkPkts * 2, 0) != hipSuccess) {
+            hipHostMalloc((void **)&P.h_out2[s], kChunkPkts * 2, 0) != hipSuccess ||
+            hipHostMalloc((void **)&P.h_st[s], kChunkPkts, 0) != hipSuccess) {
             pipe_free(P);
             return WC_ENOMEM;
         }
@@ -81,10 +85,12 @@ int zc_init_locked(Device &D)
         hipHostMalloc((void **)&Z.h_len, kZcPkts * 2, fl) != hipSuccess ||
         hipHostMalloc((void **)&Z.h_out, kZcPkts * 2, fl) != hipSuccess ||
         hipHostMalloc((void **)&Z.h_out2, kZcPkts * 2, fl) != hipSuccess ||
+        hipHostMalloc((void **)&Z.h_st, kZcPkts, fl) != hipSuccess ||
         hipHostGetDevicePointer((void **)&Z.d_off, Z.h_off, 0) != hipSuccess ||
         hipHostGetDevicePointer((void **)&Z.d_len, Z.h_len, 0) != hipSuccess ||
         hipHostGetDevicePointer((void **)&Z.d_out, Z.h_out, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&Z.d_out2, Z.h_out2, 0) != hipSuccess)
+        hipHostGetDevicePointer((void **)&Z.d_out2, Z.h_out2, 0) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&Z.d_st, Z.h_st, 0) != hipSuccess)
         return WC_ENOMEM;
     Z.ready = true;
     return WC_OK;
@@ -145,10 +151,15 @@ int out_size(int kind) { return kind == kKindRx ? 1 : 2; }
 // checksums go to d_out_hdr).
 int run_ragged_any(Device &D, const Config &C, const uint8_t *d_base, const uint64_t *d_off,
                    const uint16_t *d_len, uint64_t n, void *d_out, int kind, bool zero_copy,
-                   hipStream_t st, uint16_t *d_out_hdr = nullptr)
+                   hipStream_t st, uint16_t *d_out_hdr = nullptr, uint8_t *d_st = nullptr)
 {
     if (kind == kKindRx)
         return hip_err(rx_launch(D, C, d_base, d_off, d_len, n, (uint8_t *)d_out, nullptr, st));
+    if (kind_is_tx(kind)) // compute only: the calling thread makes the stores (wc_rt_tx.cpp)
+        return hip_err(wc::launch_tx_seal(
+            const_cast<uint8_t *>(d_base), d_off, d_len, n,
+            wc::kTxNoStore | (kind == kKindTxZero ? wc::kTxZeroUdp : 0u), d_st, d_out_hdr,
+            (uint16_t *)d_out, nullptr, C.nt != 0, st));
     const bool fused = kind == kKindFused;
     const int k = fused ? WC_CKSUM_PAYLOAD : kind;
     const Plan p = plan_ragged(D, C, n, k, zero_copy, fused);
@@ -161,7 +172,7 @@ int run_ragged_any(Device &D, const Config &C, const uint8_t *d_base, const uint
 // Small registered batch: one launch reading host memory in place.
 int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
                    const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                   uint16_t *h_out2)
+                   uint16_t *h_out2, uint8_t *h_st)
 {
     int rc = zc_init_locked(D);
     if (rc)
@@ -170,15 +181,17 @@ int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
     memcpy(Z.h_off, h_off, n * 8);
     memcpy(Z.h_len, h_len, n * 2);
     rc = run_ragged_any(D, g_cfg, dbase, Z.d_off, Z.d_len, n, Z.d_out, kind, true, Z.st,
-                        Z.d_out2);
+                        Z.d_out2, Z.d_st);
     if (rc)
         return rc;
     hipError_t e = hipStreamSynchronize(Z.st);
     if (e != hipSuccess)
         return hip_err(e);
     memcpy(h_out, (const void *)Z.h_out, n * out_size(kind));
-    if (kind == kKindFused)
+    if (kind == kKindFused || kind_is_tx(kind))
         memcpy(h_out2, (const void *)Z.h_out2, n * 2);
+    if (kind_is_tx(kind))
+        memcpy(h_st, (const void *)Z.h_st, n);
     return WC_OK;
 }
 
@@ -195,10 +208,12 @@ int zs_init_locked(Device &D)
              hipHostMalloc((void **)&S.h_len[b], kZsPkts * 2, fl) == hipSuccess &&
              hipHostMalloc((void **)&S.h_out[b], kZsPkts * 2, fl) == hipSuccess &&
              hipHostMalloc((void **)&S.h_out2[b], kZsPkts * 2, fl) == hipSuccess &&
+             hipHostMalloc((void **)&S.h_st[b], kZsPkts, fl) == hipSuccess &&
              hipHostGetDevicePointer((void **)&S.d_off[b], S.h_off[b], 0) == hipSuccess &&
              hipHostGetDevicePointer((void **)&S.d_len[b], S.h_len[b], 0) == hipSuccess &&
              hipHostGetDevicePointer((void **)&S.d_out[b], S.h_out[b], 0) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&S.d_out2[b], S.h_out2[b], 0) == hipSuccess;
+             hipHostGetDevicePointer((void **)&S.d_out2[b], S.h_out2[b], 0) == hipSuccess &&
+             hipHostGetDevicePointer((void **)&S.d_st[b], S.h_st[b], 0) == hipSuccess;
     if (!ok) {
         zs_free(S);
         return WC_ENOMEM;
@@ -218,6 +233,7 @@ void zs_free(ZcStream &S)
         (void)hipHostFree(S.h_len[b]);
         (void)hipHostFree(S.h_out[b]);
         (void)hipHostFree(S.h_out2[b]);
+        (void)hipHostFree(S.h_st[b]);
     }
     if (S.st)
         (void)hipStreamDestroy(S.st);
@@ -229,7 +245,7 @@ void zs_free(ZcStream &S)
 // lengths into the other buffer and copies chunk k - 1's results out.
 int host_zc_stream(Device &D, const uint8_t *dbase, const uint64_t *h_off,
                    const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                   uint16_t *h_out2)
+                   uint16_t *h_out2, uint8_t *h_st)
 {
     int rc = zs_init_locked(D);
     if (rc)
@@ -245,8 +261,10 @@ int host_zc_stream(Device &D, const uint8_t *dbase, const uint64_t *h_off,
         if (e != hipSuccess)
             return hip_err(e);
         memcpy(h_out + pend_lo[b] * osz, (const void *)S.h_out[b], pend_n[b] * osz);
-        if (kind == kKindFused)
+        if (kind == kKindFused || kind_is_tx(kind))
             memcpy(h_out2 + pend_lo[b], (const void *)S.h_out2[b], pend_n[b] * 2);
+        if (kind_is_tx(kind))
+            memcpy(h_st + pend_lo[b], (const void *)S.h_st[b], pend_n[b]);
         pend[b] = false;
         return WC_OK;
     };
@@ -260,7 +278,7 @@ int host_zc_stream(Device &D, const uint8_t *dbase, const uint64_t *h_off,
         memcpy(S.h_off[b], h_off + i, cnt * 8);
         memcpy(S.h_len[b], h_len + i, cnt * 2);
         rc = run_ragged_any(D, g_cfg, dbase, S.d_off[b], S.d_len[b], cnt, S.d_out[b], kind, true,
-                            S.st, S.d_out2[b]);
+                            S.st, S.d_out2[b], S.d_st[b]);
         if (rc == WC_OK)
             rc = hip_err(hipEventRecord(S.done[b], S.st));
         if (rc == WC_OK) {
@@ -416,8 +434,10 @@ int PipeRun::drain(int s)
         return hip_err(e);
     const int osz = out_size(kind);
     memcpy(h_out + pend_lo[s] * osz, P->h_out[s], pend_n[s] * osz);
-    if (kind == kKindFused)
+    if (kind == kKindFused || kind_is_tx(kind))
         memcpy(h_out2 + pend_lo[s], P->h_out2[s], pend_n[s] * 2);
+    if (kind_is_tx(kind))
+        memcpy(h_st + pend_lo[s], P->h_st[s], pend_n[s]);
     pend[s] = false;
     return WC_OK;
 }
@@ -499,14 +519,16 @@ int PipeRun::step()
     if (e != hipSuccess)
         return hip_err(e);
     rc = run_ragged_any(*D, g_cfg, P->d_bytes[slot], P->d_off[slot], P->d_len[slot], cnt,
-                        P->d_out[slot], kind, false, st, P->d_out2[slot]);
+                        P->d_out[slot], kind, false, st, P->d_out2[slot], P->d_st[slot]);
     if (rc)
         return rc;
     e = hipMemcpyAsync(P->h_out[slot], P->d_out[slot], cnt * out_size(kind),
                        hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && kind == kKindFused)
+    if (e == hipSuccess && (kind == kKindFused || kind_is_tx(kind)))
         e = hipMemcpyAsync(P->h_out2[slot], P->d_out2[slot], cnt * 2, hipMemcpyDeviceToHost,
                            st);
+    if (e == hipSuccess && kind_is_tx(kind))
+        e = hipMemcpyAsync(P->h_st[slot], P->d_st[slot], cnt, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipEventRecord(P->done[slot], st);
     if (e != hipSuccess)
@@ -567,7 +589,7 @@ void shard_range(uint64_t n, int g, int G, uint64_t *lo, uint64_t *hi)
 
 int host_pipeline(Device &D, const uint8_t *hb, bool registered, bool ascending,
                   const uint64_t *h_off, const uint16_t *h_len, uint64_t n,
-                  uint8_t *h_out, int kind, uint16_t *h_out2)
+                  uint8_t *h_out, int kind, uint16_t *h_out2, uint8_t *h_st)
 {
     PipeRun r;
     r.D = &D;
@@ -579,6 +601,7 @@ int host_pipeline(Device &D, const uint8_t *hb, bool registered, bool ascending,
     r.h_len = h_len;
     r.h_out = h_out;
     r.h_out2 = h_out2;
+    r.h_st = h_st;
     r.kind = kind;
     r.hi = n;
     while (!r.done()) {
@@ -596,12 +619,13 @@ int host_pipeline(Device &D, const uint8_t *hb, bool registered, bool ascending,
 // for a small registered batch, else the pipeline.  h_out2: the fused pair's
 // header checksums.
 int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
-               const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-               uint16_t *h_out2 = nullptr)
+               const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind, uint16_t *h_out2,
+               uint8_t *h_st)
 {
     if (n == 0)
         return WC_OK;
-    if (!h_base || !h_off || !h_len || !h_out || (kind == kKindFused && !h_out2))
+    if (!h_base || !h_off || !h_len || !h_out || (kind == kKindFused && !h_out2) ||
+        (kind_is_tx(kind) && (!h_out2 || !h_st)))
         return WC_EINVAL;
     bool ascending = true;
     uint64_t total = 0, range = 0;
@@ -618,7 +642,8 @@ int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
     if (rc)
         return rc;
     const uint8_t *dbase = registered_dptr_locked(h_base, h_bytes);
-    if (dbase && g_cfg.serve && server_enabled_locked() && n <= (uint64_t)g_cfg.serve_max) {
+    if (dbase && !kind_is_tx(kind) && g_cfg.serve && server_enabled_locked() &&
+        n <= (uint64_t)g_cfg.serve_max) {
         bool fits = true; // (a fused header adds at most 40 bytes to the span)
         for (uint64_t i = 0; i < n && fits; ++i)
             fits = span_of(h_len[i], kind) + (kind == kKindFused ? 40u : 0u) <= wc::kSrvMaxBytes;
@@ -630,21 +655,21 @@ int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
         }
     }
     if (dbase && n <= kZcPkts && total <= (uint64_t)g_cfg.zc_bytes)
-        return host_zero_copy(*D, dbase, h_off, h_len, n, h_out, kind, h_out2);
+        return host_zero_copy(*D, dbase, h_off, h_len, n, h_out, kind, h_out2, h_st);
     // A large registered batch: sparse or in any order, the kernels read its
     // packets in place (only the lines they touch cross the link); dense and
     // ascending, the pipeline's range DMA is a little faster (C2 bytes from a
     // registered region: 54.5 vs 52.9 GB/s, the three sparse ring calls 39 ->
     // 46-47 GB/s: profiles/e2e_r06b.log).
     if (dbase && g_cfg.zc_stream && (sparse || !ascending))
-        return host_zc_stream(*D, dbase, h_off, h_len, n, h_out, kind, h_out2);
+        return host_zc_stream(*D, dbase, h_off, h_len, n, h_out, kind, h_out2, h_st);
     rc = pipe_init_locked(D->pipe);
     if (rc)
         return rc;
     // (pageable and sparse: gathered packet by packet into the staging, not
     // the whole range with its gaps)
     return host_pipeline(*D, (const uint8_t *)h_base, dbase != nullptr, ascending && !sparse,
-                         h_off, h_len, n, h_out, kind, h_out2);
+                         h_off, h_len, n, h_out, kind, h_out2, h_st);
 }
 
 } // namespace rt
