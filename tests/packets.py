@@ -209,3 +209,17 @@ def pack(pkts: list[tuple[bytes, int]], align: int = 1, lead: int = 0):
     parts.append(b"\x00" * 64)
     buf = np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
     return buf, np.array(offs, dtype=np.uint64), np.array(lens, dtype=np.uint16)
+
+
+def slot_ring(frames, slot: int = 2048, rng=None, pad: int = 64):
+    """Frames in `slot`-byte buffers (netmap_slot buf_idx order scrambled)."""
+    n = len(frames)
+    idx = np.arange(n) if rng is None else rng.permutation(n)
+    buf = np.zeros(n * slot + pad, dtype=np.uint8)
+    offs = (idx * slot).astype(np.uint64)
+    lens = np.empty(n, dtype=np.uint16)
+    for i, (fr, flen) in enumerate(frames):
+        o = int(offs[i])
+        buf[o:o + len(fr)] = np.frombuffer(fr, np.uint8)
+        lens[i] = flen
+    return buf, offs, lens

@@ -14,27 +14,13 @@ import torch
 
 import warpcore_amd as wc
 from oracle import c_oracle
-from packets import RX_CASES, pack, rx_ring
+from packets import RX_CASES, pack, rx_ring, slot_ring
 
 pytestmark = pytest.mark.gpu
 
 
 def dev(a: np.ndarray, d) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(d)
-
-
-def slot_ring(frames, slot: int = 2048, rng=None, pad: int = 64):
-    """Frames in `slot`-byte buffers (netmap_slot buf_idx order scrambled)."""
-    n = len(frames)
-    idx = np.arange(n) if rng is None else rng.permutation(n)
-    buf = np.zeros(n * slot + pad, dtype=np.uint8)
-    offs = (idx * slot).astype(np.uint64)
-    lens = np.empty(n, dtype=np.uint16)
-    for i, (fr, flen) in enumerate(frames):
-        o = int(offs[i])
-        buf[o:o + len(fr)] = np.frombuffer(fr, np.uint8)
-        lens[i] = flen
-    return buf, offs, lens
 
 
 RX_MODES = {"default": {}, "ht": {"WC_RX_ADAPT": "0"},

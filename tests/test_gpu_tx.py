@@ -15,7 +15,8 @@ import torch
 import tx_model
 import warpcore_amd as wc
 from oracle import c_oracle
-from packets import RX_CASES, ipv4_udp, eth_frame, pack, rx_ring
+from packets import (RX_CASES, eth_frame, finish_udp, ipv4_udp, ipv6_udp, pack, rx_frame, rx_ring,
+                     slot_ring)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,20 +27,6 @@ CASES_OPT_FIRST = ("ok4opt",) + tuple(c for c in RX_CASES if c != "ok4opt")
 
 def dev(a: np.ndarray, d) -> torch.Tensor:
     return torch.from_numpy(np.array(a, copy=True)).to(d)  # (the shared layouts are read-only)
-
-
-def slot_ring(frames, slot: int = 2048, rng=None, pad: int = 64):
-    """Frames in `slot`-byte buffers (netmap_slot buf_idx order scrambled)."""
-    n = len(frames)
-    idx = np.arange(n) if rng is None else rng.permutation(n)
-    buf = np.zeros(n * slot + pad, dtype=np.uint8)
-    offs = (idx * slot).astype(np.uint64)
-    lens = np.empty(n, dtype=np.uint16)
-    for i, (fr, flen) in enumerate(frames):
-        o = int(offs[i])
-        buf[o:o + len(fr)] = np.frombuffer(fr, np.uint8)
-        lens[i] = flen
-    return buf, offs, lens
 
 
 LAYOUTS = ("slots", "pack_1_0", "pack_1_5", "pack_2_14", "pack_16_3")
@@ -212,6 +199,54 @@ def test_seal_tile_edges(gpu, n):
         e = tx_model.Expect(buf, offs, lens)
         assert e.seals[0].hl > 20 and e.status[0] == wc.TX_SEALED
         assert_sealed(seal(buf, offs, lens, gpu), e, f"n={n} packed={packed}")
+
+
+SEAM_IHL = (5, 9, 10, 11, 15)  # hl 40 is the last one-round header, 44 the first two-round one
+
+
+@functools.lru_cache(maxsize=None)
+def seam_frames():
+    """Valid IPv4 UDP frames at each IHL of SEAM_IHL and IPv6 ones, payloads of
+    1 and 18 bytes (the UDP fields in the frame's chunk 2, 3 or 4, the checked
+    range odd and even), two of each; then one ihl_small frame.  Returns the
+    frames and the header length of each but the last."""
+    rng = np.random.default_rng(4044)
+    frames, hls = [], []
+    for _ in range(2):
+        for plen in (1, 18):
+            payload = rng.integers(0, 256, plen, dtype=np.uint8).tobytes()
+            for ihl in SEAM_IHL:
+                fr = eth_frame(finish_udp(ipv4_udp(payload, rng, ihl=ihl)[0]), rng)
+                frames.append((fr, len(fr)))
+                hls.append(4 * ihl)
+            fr = eth_frame(finish_udp(ipv6_udp(payload, rng)[0]), rng, 0x86DD)
+            frames.append((fr, len(fr)))
+            hls.append(40)
+    frames.append(rx_frame(rng, "ihl_small", max_payload=18))
+    return frames, hls
+
+
+@pytest.mark.parametrize("phase", range(16))
+def test_parse_seam_every_phase(gpu, phase):
+    """The boundary between the one-round and the two-round header parse
+    (IHL 10 | 11) with every frame of the buffer starting at byte `phase` of a
+    16-byte chunk: the RX verdicts equal the oracle's, and the seal of the
+    same frames with their fields garbled is byte-exact."""
+    frames, hls = seam_frames()
+    buf, offs, lens = pack(frames, align=16)  # (pack aligns after its lead: shift the buffer)
+    buf, offs = np.concatenate([np.zeros(phase, np.uint8), buf]), offs + np.uint64(phase)
+    assert (offs % 16 == phase).all() and len(frames) < 64
+    want = c_oracle.rx_verdict_ragged(buf, offs, lens)
+    assert np.isin(want[:-1], (wc.RX_OK, wc.RX_OK_NO_CKSUM)).all() and wc.RX_OK in want
+    got, drops = wc.rx_verdict_ragged(dev(buf, gpu), dev(offs, gpu), dev(lens, gpu))
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    assert int(drops.item()) == int(np.isin(want, wc.RX_DROPS).sum())
+
+    tx_model.garble_fields(buf, offs, lens, np.random.default_rng(phase))
+    e = tx_model.Expect(buf, offs, lens)
+    assert (e.status[:-1] == wc.TX_SEALED).all() and e.status[-1] == wc.TX_MALFORMED
+    assert [s.hl for s in e.seals[:-1]] == hls
+    assert_sealed(seal(buf, offs, lens, gpu), e, f"phase={phase}")
 
 
 def test_seal_jumbo_frames(gpu):

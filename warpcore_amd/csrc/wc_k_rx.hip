@@ -23,6 +23,11 @@
 //      stream of the seg path (wc_seg.h, seg_tile over the tile's IP packets
 //      [ip, ip + udp_len + hl) in packet order), the payload_cksum lanes it
 //      can't take redone exactly by their own lane.
+// Steps 1 and 2 (frame_hdr, frame_hdr_slow) and the stream of step 3 where it
+// carries the checked frames only (frame_payload_cksum) are the TX seal
+// kernel's too and live in wc_rx_hdr.h; this file keeps the decision chain
+// (rx_decide), the transposed header load and the stream that starts before
+// the parse is done.
 // Every load stays inside its frame (chunks that overlap [frame, frame +
 // flen) only); whatever the reference would read past the frame is
 // WC_RX_TRUNCATED.  Roofline: HBM, the checked frames' bytes once.
@@ -113,16 +118,12 @@ __device__ __forceinline__ RxParse rx_decide(uint64_t fa, uint32_t flen, bool va
     return h;
 }
 
-// Steps 1 and 2 in ONE load round (rx_load of wc_rx_hdr.h, then rx_parse on
-// what it loaded): the frame's first five aligned chunks
-// (frame bytes [0, 65) at least, each chunk loaded only if it overlaps the
-// frame) hold the Ethernet header, an IPv4 header of up to 40 bytes or the
-// IPv6 header, and the UDP length / checksum fields after either.  A lane
-// with a longer IPv4 header (options > 20 B) or a malformed IHL < 5 sets
-// `slow` and is re-parsed by rx_parse_slow.  Two dependent load rounds per tile cost the mixed-size ring
-// its headroom over payload_cksum alone.
+// Steps 1 and 2 in ONE load round (rx_load, then frame_hdr on what it loaded:
+// wc_rx_hdr.h), the lanes it can't take re-parsed by rx_parse_slow: two
+// dependent load rounds per tile cost the mixed-size ring its headroom over
+// payload_cksum alone.
 //
-// The same five chunks, loaded transposed (HT): instruction i reads frames
+// rx_load's five chunks, loaded transposed (HT): instruction i reads frames
 // 16 i .. 16 i + 15, four lanes per frame, lane 4 f' + j its chunk j -- 64
 // contiguous bytes per frame, one cache line instead of four separate
 // 16-byte requests (five one-lane-per-frame loads put 320 line requests per
@@ -184,92 +185,29 @@ __device__ __forceinline__ void rx_hdr_gather(u32x4 *stage, int lane, const u32x
     wave_order(); // stage is rewritten by the stream's first row group
 }
 
+// The one-round parse (frame_hdr, wc_rx_hdr.h) and the decision on it.  `slow`:
+// an IPv4 header longer than 40 bytes (options > 20 B) is not inside the five
+// chunks; and for a malformed IHL < 5 ip4_rx still rules on ip_cksum(ip, hl)
+// (ip4.c:111), a sum over fewer than the 20 bytes frame_hdr always takes --
+// both are parsed again by rx_parse_slow.  (The TX seal rules IHL < 5
+// MALFORMED before the header sum matters: tx_parse asks for hl > 40 only.)
 __device__ __forceinline__ RxParse rx_parse(const u32x4 (&c)[5], uint64_t fa, uint32_t flen,
                                             bool valid, bool &slow)
 {
-    const uint32_t sf = (uint32_t)(fa & 15u);
-    // frame bytes 12..23 start in chunk 0 or 1
-    const uint32_t o1 = sf + 12u;
-    const bool j1 = o1 >= 16u;
-    const u32x4 x1 = j1 ? c[1] : c[0], y1 = j1 ? c[2] : c[1];
-    uint32_t fw[3];
-    win_rot(x1, y1, y1, o1 & 15u, fw);
-    const RxHdr x = rx_hdr(fw[0], fw[1], fw[2], flen);
-    slow = valid && x.hdr_in && x.v4 && (x.hl > 40u || x.hl < 20u);
-    // UDP length / checksum at frame byte 14 + hl + 4: chunk 2, 3 or 4 (20 <= hl <= 40)
-    const uint32_t u = sf + 18u + x.hl;
-    const uint32_t ju = min(u >> 4, 4u);
-    const u32x4 z4 = {0u, 0u, 0u, 0u};
-    const u32x4 xu = ju <= 2u ? c[2] : (ju == 3u ? c[3] : c[4]);
-    const u32x4 yu = ju <= 2u ? c[3] : (ju == 3u ? c[4] : z4);
-    const uint32_t g0 = win_bytes(xu, yu, yu, u & 15u, 0);
-    // ip_cksum(ip, hl) (ip4.c:110-115) over frame bytes [14, 14 + hl),
-    // 20 <= hl <= 40 here (14 + 40 + 15 < 80: inside the five chunks): the
-    // header's little-endian words summed header-relative, as csum_oc16 reads
-    // them (in_cksum.c:107-120) -- two 20-byte windows rotated out of the
-    // chunks, one dot2 per dword, so no address-parity fix.  (Per-chunk byte
-    // masks over all five chunks took about twice the VALU.)
-    const uint32_t o = sf + 14u;  // header start in the chunk stream: 14..29
-    const uint32_t o2 = o + 20u;  // its second 20 bytes: 34..49
-    const bool j0 = o >= 16u, j2 = o2 >= 48u;
-    uint32_t h0[5], h1[5];
-    win_rot(j0 ? c[1] : c[0], j0 ? c[2] : c[1], j0 ? c[3] : c[2], o & 15u, h0);
-    win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, h1);
-    uint32_t V = 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-        V = wsum(h0[m], V);
-#pragma unroll
-    for (int m = 0; m < 5; ++m) // header bytes 20 + 4 m .. 23 + 4 m, if below hl
-        V = wsum(x.hl > 20u + 4u * m ? h1[m] : 0u, V);
-    const uint16_t ipck = fold_not(V);
-    return rx_decide(fa, flen, valid, x, g0, ipck);
+    const FrameHdr f = frame_hdr(c, fa, flen);
+    slow = valid && f.x.hdr_in && f.x.v4 && (f.x.hl > 40u || f.x.hl < 20u);
+    return rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
 }
 
-// Steps 1 and 2 in two load rounds for this lane's frame [fa, fa + flen): the
-// chunks around frame bytes 12..23 first, then, with the IHL known, the UDP
-// fields and the IPv4 header's chunks (any IHL).  The fallback of rx_parse.
+// The fallback of rx_parse: two load rounds, any IHL (frame_hdr_slow).
 __device__ __forceinline__ RxParse rx_parse_slow(uint64_t fa, uint32_t flen, bool valid,
                                                  uint64_t zero)
 {
-    const uint64_t fend = fa + flen;
-    const uint64_t a1 = fa + 12u;
-    const Win2 w1 = win2_load(a1, fend, valid && flen > 12u, zero);
-    const uint32_t s1 = (uint32_t)(a1 & 15u);
-    uint32_t fw[3]; // frame 12..15, 16..19 = ip 2..5, 20..23 = ip 6..9
-    win_rot(w1.x, w1.y, w1.y, s1, fw);
-    const RxHdr x = rx_hdr(fw[0], fw[1], fw[2], flen);
-    const uint64_t ip = fa + 14u;
-    const uint32_t hl = x.hl;
-    // The UDP length / checksum fields (udp.h:41-46) at ip + hl + 4, and the
-    // IPv4 header's chunks, all issued before any is used.
-    const uint64_t a2 = ip + hl + 4u;
-    const Win2 w2 = win2_load(a2, fend, valid && x.udp_in, zero);
-    const bool hsum = valid && x.hdr_in && x.v4;
-    const uint32_t sip = (uint32_t)(ip & 15u);
-    const uint64_t cip = ip & ~15ull;
-    const uint32_t nh = hsum ? (sip + hl + 15u) >> 4 : 0u;
-    u32x4 hc[kHdrChunks];
-#pragma unroll
-    for (int k = 0; k < kHdrChunks; ++k)
-        hc[k] = load_chunk<false>((uint32_t)k < nh ? cip + 16ull * k : zero);
-    // ip_cksum(ip, hl) (ip4.c:110-115): word sum at even addresses; an odd
-    // start folds rotl32(V, 8) (the seg path's residue identity; <= 30 words,
-    // no wrap).
-    uint32_t V = 0;
-#pragma unroll
-    for (int k = 0; k < kHdrChunks; ++k)
-        V += seg_range(hc[k], 16 * k - (int)sip, 0, (int)hl);
-    const uint16_t ipck = fold_not((ip & 1u) ? __builtin_amdgcn_alignbit(V, V, 24) : V);
-    const uint32_t g0 = win_bytes(w2.x, w2.y, w2.y, (uint32_t)(a2 & 15u), 0);
-    return rx_decide(fa, flen, valid, x, g0, ipck);
+    const FrameHdr f = frame_hdr_slow(fa, flen, valid, zero);
+    return rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
 }
 
-
-// One 64-chunk row group of 4 rows for the gathered stream (the seg
-// kernel's ragged default; 2-row groups measured slower, 128 -> 131 us on the
-// mixed ring: profiles/ab_r04_rx_modes.log).  Kernel modes (launch_rx_verdict),
-// all giving the same verdicts:
+// Kernel modes (launch_rx_verdict), all giving the same verdicts:
 //   EARLY  the header parse completes BEFORE the stream, which then carries
 //          only the frames that need the UDP check and only their checked
 //          range [ip, ip + udp_len + hl) -- one load round trip per tile
@@ -294,31 +232,21 @@ __device__ __forceinline__ RxParse rx_parse_slow(uint64_t fa, uint32_t flen, boo
 // One-wave workgroups: a wave's slot is handed to the next tile as soon as
 // its own tile is done, not when the slowest of four is (mixed-size ring with
 // ARP frames 91.8 -> 89.1 us, the others unchanged: profiles/ab_r06m_rx_waves.log).
-constexpr int kRxWaves = 1;
 constexpr int kRxSpan = 15; // XCD super-blocks of 2^15 tiles, as the seg kernel's
 
-template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY = false>
-__global__ void __launch_bounds__(64 * kRxWaves) __attribute__((amdgpu_waves_per_eu(4)))
+template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
 k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
              const uint16_t *__restrict__ flens, uint64_t n, uint8_t *__restrict__ verdict,
              unsigned long long *__restrict__ drops, uint32_t *__restrict__ tally, uint32_t gen)
 {
-    constexpr int UNS = 4;
-    using Src = GathSrc<UNS, NT, SKIP && !EARLY>;
-    struct Lds {
-        FlatLds<UNS> f; // slot table, row marks, prefix sums
-        u32x4 stage[64 * UNS]; // also the header chunks' transpose (HT)
-        u32x4 pm[17]; // seg_head's masks
-    };
-    __shared__ Lds lds_all[kRxWaves];
+    __shared__ FrameLds L;
 
     const int lane = threadIdx.x & 63;
-    const int w = kRxWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    Lds &L = lds_all[w];
     seg_init_masks(L.pm, lane); // read after the first row group's wave_order
     const uint64_t ntiles = (n + 63) / 64;
-    const uint64_t nwaves = (uint64_t)gridDim.x * kRxWaves;
-    uint64_t tile = xcd_block(kRxSpan << 8) * kRxWaves + w; // the seg kernel's XCD span
+    const uint64_t nwaves = gridDim.x;
+    uint64_t tile = xcd_block(kRxSpan << 8);
     uint32_t ndrop = 0;
     const uint64_t zero = (uint64_t)(uintptr_t)&kZeroChunk;
 
@@ -360,20 +288,12 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
             h = rx_parse(c, fa, flen, valid, slow);
             v = h.verdict;
             const bool need = h.need && !slow;
-            if (__ballot(need)) {
-                const FlatTile t = flat_tile_setup<UNS, 1>(L.f, lane, ip, h.plen, h.plen, need, 0u);
-                bool done = true;
-                uint16_t rh = 0;
-                uint16_t r = seg_tile<UNS, WC_KIND_PAYLOAD, NT, false, Src, true>(
-                    L.f.pre, L.stage, L.pm, lane, ip, 16ull * t.cp + (ip & 15u), h.plen, need,
-                    t.total, Src{&L.f, t}, zero, done, rh);
-                if (need && !done) // header longer than the packet, or a possible wrap
-                    r = lane_payload_exact<NT>(ip, h.plen);
-                if (need)
-                    v = r != 0 ? kRxBadUdpCksum : kRxOk; // udp.c:134-139
-                wave_order(); // the tables are rewritten by the next tile
-            }
+            const uint32_t r = frame_payload_cksum<NT>(L, lane, ip, h.plen, need, zero);
+            if (need)
+                v = r != 0 ? kRxBadUdpCksum : kRxOk; // udp.c:134-139
         } else {
+            constexpr int UNS = kFrameUns;
+            using Src = GathSrc<UNS, NT, SKIP>;
             // Header chunks first; then every frame that may need the UDP
             // check (>= 28 IP bytes) streams its IP bytes [ip, ip + room) as
             // the seg path's gathered stream, and the parse completes once
@@ -449,12 +369,12 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
 
 } // namespace
 
-template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY = false>
+template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY>
 static hipError_t launch_rx_one(const void *base, const uint64_t *offs, const uint16_t *flens,
                                 uint64_t n, uint8_t *verdict, uint64_t *drops, int grid,
                                 hipStream_t st, uint32_t *tally, uint32_t gen)
 {
-    hipLaunchKernelGGL((k_rx_verdict<NT, EARLY, HT, SKIP, TALLY>), dim3(grid), dim3(64 * kRxWaves), 0, st,
+    hipLaunchKernelGGL((k_rx_verdict<NT, EARLY, HT, SKIP, TALLY>), dim3(grid), dim3(64), 0, st,
                        (const uint8_t *)base, offs, flens, n, verdict,
                        (unsigned long long *)drops, tally, gen);
     return hipGetLastError();
@@ -470,33 +390,21 @@ hipError_t launch_rx_verdict(const void *base, const uint64_t *offs, const uint1
     // grid, each wave then walks several tiles with the next tile's metadata
     // prefetched.
     const uint64_t cap = max_grid > 0 ? (uint64_t)max_grid : kMaxGridBlocks;
-    const int grid = (int)std::min<uint64_t>(
-        cap, std::max<uint64_t>(1, (tiles + kRxWaves - 1) / kRxWaves));
+    const int grid = (int)std::min<uint64_t>(cap, std::max<uint64_t>(1, tiles));
     // EARLY streams only the checked frames: SKIP has nothing to skip there,
     // and is dropped so that NT and HDRT are still honoured.
     const bool early = mode & kRxEarly, ht = mode & kRxHdrT, skip = (mode & kRxSkip) && !early;
-    if (tally && !skip && ht) { // ADAPT: the host chose EARLY or HT; the kernel tallies
-        if (nt)
-            return early ? launch_rx_one<true, true, true, false, true>(base, offs, flens, n,
-                                                                        verdict, drops, grid,
-                                                                        st, tally, gen)
-                         : launch_rx_one<true, false, true, false, true>(base, offs, flens, n,
-                                                                         verdict, drops, grid,
-                                                                         st, tally, gen);
-        return early ? launch_rx_one<false, true, true, false, true>(base, offs, flens, n, verdict,
-                                                                     drops, grid, st, tally, gen)
-                     : launch_rx_one<false, false, true, false, true>(base, offs, flens, n,
-                                                                      verdict, drops, grid, st,
-                                                                      tally, gen);
-    }
-#define WC_RX(N, E, H, S)                                                      \
-    if (nt == N && early == E && ht == H && skip == S)                         \
-        return launch_rx_one<N, E, H, S>(base, offs, flens, n, verdict, drops, grid, st,   \
-                                         nullptr, 0u);
+    // ADAPT: the host chose EARLY or HT; the kernel tallies
+    const bool tal = tally && !skip && ht;
+#define WC_RX(N, E, H, S, T)                                                   \
+    if (nt == N && early == E && ht == H && skip == S && tal == T)             \
+        return launch_rx_one<N, E, H, S, T>(base, offs, flens, n, verdict, drops, grid, st,   \
+                                            T ? tally : nullptr, T ? gen : 0u);
 #define WC_RX_NT(N)                                                            \
-    WC_RX(N, false, false, false) WC_RX(N, false, false, true)                 \
-    WC_RX(N, false, true, false) WC_RX(N, false, true, true)                   \
-    WC_RX(N, true, false, false) WC_RX(N, true, true, false)
+    WC_RX(N, false, false, false, false) WC_RX(N, false, false, true, false)   \
+    WC_RX(N, false, true, false, false) WC_RX(N, false, true, true, false)     \
+    WC_RX(N, true, false, false, false) WC_RX(N, true, true, false, false)     \
+    WC_RX(N, false, true, false, true) WC_RX(N, true, true, false, true)
     WC_RX_NT(true)
     WC_RX_NT(false)
 #undef WC_RX_NT

@@ -9,18 +9,21 @@
 //   udp_tx      /root/reference/lib/src/udp.c:209-213   udp->cksum = 0, then
 //               (unless the socket sends zero checksums) udp->cksum =
 //               payload_cksum(ip, hl + udp_len), a computed 0 stored as 0
-// The field reads and their order are the RX chain's (wc_k_rx.hip, the header
-// view of wc_rx_hdr.h); the codes are enum wc_tx_status (wc_cksum.h).
+// The field reads and their order are the RX chain's (wc_k_rx.hip); the codes
+// are enum wc_tx_status (wc_cksum.h).  The header parse and the gathered
+// stream are the RX kernel's own code (wc_rx_hdr.h); this file keeps the
+// decision chain (tx_decide) and the stores.
 //
 // One wave per tile of 64 frames (lane l = frame l), one-shot grid, the RX
 // kernel's EARLY structure:
 //   1. the frame's first five aligned chunks, each only where it overlaps the
 //      frame: every header field, the IPv4 header's sum (up to 40 bytes) and
-//      the UDP length -- the status is final here;
+//      the UDP length (frame_hdr) -- the status is final here;
 //   2. the frames whose UDP checksum is computed go through the gathered
-//      stream of the seg path (seg_tile over [ip, ip + hl + udp_len)), the
-//      lanes it can't take redone by lane_payload_exact; IPv4 headers longer
-//      than 40 bytes take a per-lane path of their own (tx_parse_slow);
+//      stream of the seg path (frame_payload_cksum: seg_tile over [ip, ip +
+//      hl + udp_len), the lanes it can't take redone by lane_payload_exact);
+//      IPv4 headers longer than 40 bytes take a per-lane path of their own
+//      (tx_parse_slow, frame_hdr_slow);
 //   3. with every load of the tile's frames back (s_waitcnt vmcnt(0)), each
 //      lane stores its one or two fields: one 2-byte store at an even address,
 //      two byte stores at an odd one.
@@ -115,79 +118,24 @@ __device__ __forceinline__ TxParse tx_decide(uint32_t flen, bool valid, const Rx
     return h;
 }
 
-// The parse on the five chunks of rx_load: header fields, ip_cksum(ip, hl)
-// for 20 <= hl <= 40 (two 20-byte windows rotated out of the chunks, summed
-// header-relative as csum_oc16 reads them) and the UDP length / checksum
-// fields.  An IPv4 header longer than 40 bytes sets `slow` (tx_parse_slow).
+// The one-round parse (frame_hdr, wc_rx_hdr.h) and the decision on it.  `slow`:
+// an IPv4 header longer than 40 bytes is not inside the five chunks
+// (tx_parse_slow).  Unlike the RX kernel's rx_parse, IHL < 5 does not ask for
+// it: tx_decide rules such a header MALFORMED without looking at its sum.
 __device__ __forceinline__ TxParse tx_parse(const u32x4 (&c)[5], uint64_t fa, uint32_t flen,
                                             bool valid, bool zero_udp, bool &slow)
 {
-    const uint32_t sf = (uint32_t)(fa & 15u);
-    // frame bytes 12..23 start in chunk 0 or 1
-    const uint32_t o1 = sf + 12u;
-    const bool j1 = o1 >= 16u;
-    const u32x4 x1 = j1 ? c[1] : c[0], y1 = j1 ? c[2] : c[1];
-    uint32_t fw[3];
-    win_rot(x1, y1, y1, o1 & 15u, fw);
-    const RxHdr x = rx_hdr(fw[0], fw[1], fw[2], flen);
-    slow = valid && x.hdr_in && x.v4 && x.hl > 40u;
-    // UDP length / checksum at frame byte 14 + hl + 4: chunk 2, 3 or 4 (20 <= hl <= 40)
-    const uint32_t u = sf + 18u + x.hl;
-    const uint32_t ju = min(u >> 4, 4u);
-    const u32x4 z4 = {0u, 0u, 0u, 0u};
-    const u32x4 xu = ju <= 2u ? c[2] : (ju == 3u ? c[3] : c[4]);
-    const u32x4 yu = ju <= 2u ? c[3] : (ju == 3u ? c[4] : z4);
-    const uint32_t g0 = win_bytes(xu, yu, yu, u & 15u, 0);
-    const uint32_t o = sf + 14u;  // header start in the chunk stream: 14..29
-    const uint32_t o2 = o + 20u;  // its second 20 bytes: 34..49
-    const bool j0 = o >= 16u, j2 = o2 >= 48u;
-    uint32_t h0[5], h1[5];
-    win_rot(j0 ? c[1] : c[0], j0 ? c[2] : c[1], j0 ? c[3] : c[2], o & 15u, h0);
-    win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, h1);
-    uint32_t V = 0;
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-        V = wsum(h0[m], V);
-#pragma unroll
-    for (int m = 0; m < 5; ++m) // header bytes 20 + 4 m .. 23 + 4 m, if below hl
-        V = wsum(x.hl > 20u + 4u * m ? h1[m] : 0u, V);
-    // ip->cksum: header bytes 10..11, the upper half of header dword 2
-    return tx_decide(flen, valid, x, g0, fold_not(V), h0[2] >> 16, zero_udp);
+    const FrameHdr f = frame_hdr(c, fa, flen);
+    slow = valid && f.x.hdr_in && f.x.v4 && f.x.hl > 40u;
+    return tx_decide(flen, valid, f.x, f.g0, f.ipck, f.f_ip, zero_udp);
 }
 
-// The same in two load rounds for this lane's frame, any IHL: the chunks
-// around frame bytes 12..23 first, then, with the IHL known, the UDP fields
-// and the IPv4 header's chunks (word sum at even addresses; an odd start
-// folds rotl32(V, 8), the seg path's residue identity).
+// The fallback of tx_parse: two load rounds, any IHL (frame_hdr_slow).
 __device__ __forceinline__ TxParse tx_parse_slow(uint64_t fa, uint32_t flen, bool valid,
                                                  bool zero_udp, uint64_t zero)
 {
-    const uint64_t fend = fa + flen;
-    const uint64_t a1 = fa + 12u;
-    const Win2 w1 = win2_load(a1, fend, valid && flen > 12u, zero);
-    uint32_t fw[3]; // frame 12..15, 16..19 = ip 2..5, 20..23 = ip 6..9
-    win_rot(w1.x, w1.y, w1.y, (uint32_t)(a1 & 15u), fw);
-    const RxHdr x = rx_hdr(fw[0], fw[1], fw[2], flen);
-    const uint64_t ip = fa + 14u;
-    const uint32_t hl = x.hl;
-    const uint64_t a2 = ip + hl + 4u;
-    const Win2 w2 = win2_load(a2, fend, valid && x.udp_in, zero);
-    const bool hsum = valid && x.hdr_in && x.v4;
-    const uint32_t sip = (uint32_t)(ip & 15u);
-    const uint64_t cip = ip & ~15ull;
-    const uint32_t nh = hsum ? (sip + hl + 15u) >> 4 : 0u;
-    u32x4 hc[kHdrChunks];
-#pragma unroll
-    for (int k = 0; k < kHdrChunks; ++k)
-        hc[k] = load_chunk<false>((uint32_t)k < nh ? cip + 16ull * k : zero);
-    uint32_t V = 0;
-#pragma unroll
-    for (int k = 0; k < kHdrChunks; ++k)
-        V += seg_range(hc[k], 16 * k - (int)sip, 0, (int)hl);
-    const uint32_t ipck = fold_not((ip & 1u) ? __builtin_amdgcn_alignbit(V, V, 24) : V);
-    const uint32_t f_ip = win_bytes(hc[0], hc[1], hc[2], sip, 2) >> 16; // header bytes 10..11
-    const uint32_t g0 = win_bytes(w2.x, w2.y, w2.y, (uint32_t)(a2 & 15u), 0);
-    return tx_decide(flen, valid, x, g0, ipck, f_ip, zero_udp);
+    const FrameHdr f = frame_hdr_slow(fa, flen, valid, zero);
+    return tx_decide(flen, valid, f.x, f.g0, f.ipck, f.f_ip, zero_udp);
 }
 
 typedef uint16_t __attribute__((address_space(1))) *gu16_ptr;
@@ -217,14 +165,7 @@ k_tx_seal(uint8_t *base, const uint64_t *__restrict__ offs,
           uint8_t *__restrict__ status, uint16_t *__restrict__ out_ip,
           uint16_t *__restrict__ out_udp, unsigned long long *__restrict__ errors)
 {
-    constexpr int UNS = 4;
-    using Src = GathSrc<UNS, NT, false>;
-    struct Lds {
-        FlatLds<UNS> f; // slot table, row marks, prefix sums
-        u32x4 stage[64 * UNS];
-        u32x4 pm[17]; // seg_head's masks
-    };
-    __shared__ Lds L;
+    __shared__ FrameLds L;
 
     const int lane = threadIdx.x & 63;
     const bool zero_udp = zero_udp_flag != 0u; // wave-uniform
@@ -251,19 +192,8 @@ k_tx_seal(uint8_t *base, const uint64_t *__restrict__ offs,
         const uint64_t ip = fa + 14u;
         bool slow = false;
         TxParse h = tx_parse(c, fa, flen, valid, zero_udp, slow);
-        uint32_t r = 0; // payload_cksum(ip, plen) of the bytes as loaded (need)
-        const bool need = h.need && !slow;
-        if (__ballot(need)) {
-            const FlatTile t = flat_tile_setup<UNS, 1>(L.f, lane, ip, h.plen, h.plen, need, 0u);
-            bool done = true;
-            uint16_t rh = 0;
-            r = seg_tile<UNS, WC_KIND_PAYLOAD, NT, false, Src, true>(
-                L.f.pre, L.stage, L.pm, lane, ip, 16ull * t.cp + (ip & 15u), h.plen, need,
-                t.total, Src{&L.f, t}, zero, done, rh);
-            if (need && !done) // a possible wrap of the odd-start residue
-                r = lane_payload_exact<NT>(ip, h.plen);
-            wave_order(); // the tables are rewritten by the next tile
-        }
+        // payload_cksum(ip, plen) of the bytes as loaded (need)
+        uint32_t r = frame_payload_cksum<NT>(L, lane, ip, h.plen, h.need && !slow, zero);
         if (__ballot(slow)) { // IPv4 headers with more than 20 B of options
             const TxParse hs = tx_parse_slow(fa, flen, slow, zero_udp, zero);
             if (slow) {
@@ -319,15 +249,13 @@ hipError_t launch_tx_seal(void *base, const uint64_t *offs, const uint16_t *flen
     const int grid = (int)std::min<uint64_t>(kMaxGridBlocks, std::max<uint64_t>(1, tiles));
     const uint32_t zu = (flags & kTxZeroUdp) ? 1u : 0u;
     const bool store = !(flags & kTxNoStore);
-    if (nt)
-        return store ? launch_tx_one<true, true>(base, offs, flens, n, zu, status, out_ip, out_udp,
-                                                 errors, grid, st)
-                     : launch_tx_one<true, false>(base, offs, flens, n, zu, status, out_ip,
-                                                  out_udp, errors, grid, st);
-    return store ? launch_tx_one<false, true>(base, offs, flens, n, zu, status, out_ip, out_udp,
-                                              errors, grid, st)
-                 : launch_tx_one<false, false>(base, offs, flens, n, zu, status, out_ip, out_udp,
-                                               errors, grid, st);
+#define WC_TX(N, S)                                                            \
+    if (nt == N && store == S)                                                 \
+        return launch_tx_one<N, S>(base, offs, flens, n, zu, status, out_ip, out_udp, errors,  \
+                                   grid, st);
+    WC_TX(true, true) WC_TX(true, false) WC_TX(false, true) WC_TX(false, false)
+#undef WC_TX
+    return hipErrorInvalidValue; // (every combination is listed above)
 }
 
 } // namespace wc

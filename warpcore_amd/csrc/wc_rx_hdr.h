@@ -1,8 +1,18 @@
-// wc_rx_hdr.h -- the Ethernet / IP header view of one frame, shared by the RX
-// verdict kernel (wc_k_rx.hip) and the TX seal kernel (wc_k_tx.hip): the
-// per-frame header chunk loads that stay inside the frame, and the fields both
-// decision chains read (EtherType, version, IHL, lengths, fragment offset,
-// protocol / next header).  DESIGN.md sections 8 and 4.7.
+// wc_rx_hdr.h -- what the RX verdict kernel (wc_k_rx.hip) and the TX seal
+// kernel (wc_k_tx.hip) share about one frame, each stated once (DESIGN.md
+// sections 8 and 4.7):
+//   * the per-frame header chunk loads that stay inside the frame (win2_load,
+//     rx_load);
+//   * the header view both decision chains read (RxHdr: EtherType, version,
+//     IHL, lengths, fragment offset, protocol / next header);
+//   * the frame header parse (FrameHdr): that view, the UDP length / checksum
+//     word and ip_cksum(ip, hl) of the header as loaded -- frame_hdr over
+//     rx_load's five chunks (IPv4 headers of 20..40 bytes), frame_hdr_slow in
+//     two load rounds of its own (any IHL);
+//   * the gathered stream of a tile's frames that need the UDP sum (FrameLds,
+//     frame_payload_cksum).
+// The two decision chains themselves (rx_decide, tx_decide) restate different
+// reference functions and stay with their kernels.
 #pragma once
 
 #include "wc_seg.h"
@@ -68,6 +78,137 @@ __device__ __forceinline__ void rx_load(uint64_t fa, uint32_t flen, bool valid, 
 #pragma unroll
     for (int k = 0; k < 5; ++k)
         c[k] = load_chunk<false>(valid && cf + 16ull * k < fend ? cf + 16ull * k : zero);
+}
+
+// What either kernel's decision chain takes from the frame's headers.
+struct FrameHdr {
+    RxHdr x;
+    uint32_t g0;   // UDP length | checksum << 16 (udp.h:41-46), a native word
+    uint32_t ipck; // ip_cksum(ip, hl) of the header as loaded
+    uint32_t f_ip; // ip->cksum as loaded, a native word (the TX seal only)
+};
+
+// The parse in ONE load round, on the five chunks of rx_load (or of the RX
+// kernel's transposed rx_load_t).  Right for IPv6 and for IPv4 headers of
+// 20 <= hl <= 40 bytes; the caller sends every other frame whose header sum
+// it needs through frame_hdr_slow.
+__device__ __forceinline__ FrameHdr frame_hdr(const u32x4 (&c)[5], uint64_t fa, uint32_t flen)
+{
+    FrameHdr f;
+    const uint32_t sf = (uint32_t)(fa & 15u);
+    // frame bytes 12..23 start in chunk 0 or 1
+    const uint32_t o1 = sf + 12u;
+    const bool j1 = o1 >= 16u;
+    const u32x4 x1 = j1 ? c[1] : c[0], y1 = j1 ? c[2] : c[1];
+    uint32_t fw[3];
+    win_rot(x1, y1, y1, o1 & 15u, fw);
+    f.x = rx_hdr(fw[0], fw[1], fw[2], flen);
+    const uint32_t hl = f.x.hl;
+    // UDP length / checksum at frame byte 14 + hl + 4: chunk 2, 3 or 4 (20 <= hl <= 40)
+    const uint32_t u = sf + 18u + hl;
+    const uint32_t ju = min(u >> 4, 4u);
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 xu = ju <= 2u ? c[2] : (ju == 3u ? c[3] : c[4]);
+    const u32x4 yu = ju <= 2u ? c[3] : (ju == 3u ? c[4] : z4);
+    f.g0 = win_bytes(xu, yu, yu, u & 15u, 0);
+    // ip_cksum(ip, hl) (ip4.c:110-115) over frame bytes [14, 14 + hl),
+    // 20 <= hl <= 40 here (14 + 40 + 15 < 80: inside the five chunks): the
+    // header's little-endian words summed header-relative, as csum_oc16 reads
+    // them (in_cksum.c:107-120) -- two 20-byte windows rotated out of the
+    // chunks, one dot2 per dword, so no address-parity fix.  (Per-chunk byte
+    // masks over all five chunks took about twice the VALU.)
+    const uint32_t o = sf + 14u;  // header start in the chunk stream: 14..29
+    const uint32_t o2 = o + 20u;  // its second 20 bytes: 34..49
+    const bool j0 = o >= 16u, j2 = o2 >= 48u;
+    uint32_t h0[5], h1[5];
+    win_rot(j0 ? c[1] : c[0], j0 ? c[2] : c[1], j0 ? c[3] : c[2], o & 15u, h0);
+    win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, h1);
+    uint32_t V = 0;
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+        V = wsum(h0[m], V);
+#pragma unroll
+    for (int m = 0; m < 5; ++m) // header bytes 20 + 4 m .. 23 + 4 m, if below hl
+        V = wsum(hl > 20u + 4u * m ? h1[m] : 0u, V);
+    f.ipck = fold_not(V);
+    f.f_ip = h0[2] >> 16; // header bytes 10..11, the upper half of header dword 2
+    return f;
+}
+
+// The same in two load rounds for this lane's frame [fa, fa + flen), any IHL:
+// the chunks around frame bytes 12..23 first, then, with the IHL known, the
+// UDP fields and the IPv4 header's chunks.  The fallback of frame_hdr.
+__device__ __forceinline__ FrameHdr frame_hdr_slow(uint64_t fa, uint32_t flen, bool valid,
+                                                   uint64_t zero)
+{
+    FrameHdr f;
+    const uint64_t fend = fa + flen;
+    const uint64_t a1 = fa + 12u;
+    const Win2 w1 = win2_load(a1, fend, valid && flen > 12u, zero);
+    uint32_t fw[3]; // frame 12..15, 16..19 = ip 2..5, 20..23 = ip 6..9
+    win_rot(w1.x, w1.y, w1.y, (uint32_t)(a1 & 15u), fw);
+    f.x = rx_hdr(fw[0], fw[1], fw[2], flen);
+    const uint64_t ip = fa + 14u;
+    const uint32_t hl = f.x.hl;
+    // The UDP length / checksum fields (udp.h:41-46) at ip + hl + 4, and the
+    // IPv4 header's chunks, all issued before any is used.
+    const uint64_t a2 = ip + hl + 4u;
+    const Win2 w2 = win2_load(a2, fend, valid && f.x.udp_in, zero);
+    const bool hsum = valid && f.x.hdr_in && f.x.v4;
+    const uint32_t sip = (uint32_t)(ip & 15u);
+    const uint64_t cip = ip & ~15ull;
+    const uint32_t nh = hsum ? (sip + hl + 15u) >> 4 : 0u;
+    u32x4 hc[kHdrChunks];
+#pragma unroll
+    for (int k = 0; k < kHdrChunks; ++k)
+        hc[k] = load_chunk<false>((uint32_t)k < nh ? cip + 16ull * k : zero);
+    // ip_cksum(ip, hl) (ip4.c:110-115): word sum at even addresses; an odd
+    // start folds rotl32(V, 8) (the seg path's residue identity; <= 30 words,
+    // no wrap).
+    uint32_t V = 0;
+#pragma unroll
+    for (int k = 0; k < kHdrChunks; ++k)
+        V += seg_range(hc[k], 16 * k - (int)sip, 0, (int)hl);
+    f.ipck = fold_not((ip & 1u) ? __builtin_amdgcn_alignbit(V, V, 24) : V);
+    f.f_ip = win_bytes(hc[0], hc[1], hc[2], sip, 2) >> 16; // header bytes 10..11
+    f.g0 = win_bytes(w2.x, w2.y, w2.y, (uint32_t)(a2 & 15u), 0);
+    return f;
+}
+
+// One 64-chunk row group of 4 rows for the gathered stream (the seg kernel's
+// ragged default; 2-row groups measured slower, 128 -> 131 us on the mixed
+// ring: profiles/ab_r04_rx_modes.log).
+constexpr int kFrameUns = 4;
+
+// A wave's LDS for one tile of 64 frames.
+struct FrameLds {
+    FlatLds<kFrameUns> f;        // slot table, row marks, prefix sums
+    u32x4 stage[64 * kFrameUns]; // (RX: also the header chunks' transpose)
+    u32x4 pm[17];                // seg_head's masks
+};
+
+// payload_cksum(ip, plen) for the tile's lanes with `need` (the other lanes'
+// result means nothing): their packets [ip, ip + plen), and nothing else, as one gathered stream of
+// the seg path, the lanes it can't take (header longer than the packet, a
+// possible wrap of the odd-start residue) redone exactly by their own lane.
+template <bool NT>
+__device__ __forceinline__ uint32_t frame_payload_cksum(FrameLds &L, int lane, uint64_t ip,
+                                                        uint32_t plen, bool need, uint64_t zero)
+{
+    using Src = GathSrc<kFrameUns, NT, false>;
+    uint32_t r = 0;
+    if (__ballot(need)) {
+        const FlatTile t = flat_tile_setup<kFrameUns, 1>(L.f, lane, ip, plen, plen, need, 0u);
+        bool done = true;
+        uint16_t rh = 0;
+        r = seg_tile<kFrameUns, WC_KIND_PAYLOAD, NT, false, Src, true>(
+            L.f.pre, L.stage, L.pm, lane, ip, 16ull * t.cp + (ip & 15u), plen, need, t.total,
+            Src{&L.f, t}, zero, done, rh);
+        if (need && !done)
+            r = lane_payload_exact<NT>(ip, plen);
+        wave_order(); // the tables are rewritten by the next tile
+    }
+    return r;
 }
 
 } // namespace
