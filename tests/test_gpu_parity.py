@@ -6,6 +6,7 @@ configurations C2 (2^20 x 1472 B), C3 (MTU sweep x 2^20) and C4 (2^24 Zipf
 packets, packed unaligned) are checked in full against the multi-threaded C
 oracle.
 """
+import functools
 import json
 import subprocess
 from pathlib import Path
@@ -14,9 +15,12 @@ import numpy as np
 import pytest
 import torch
 
+import tx_model
 import warpcore_amd as wc
 from oracle import c_oracle, py_oracle
-from packets import insert_checksum, ipv4_udp, ipv6_udp, pack, random_packets
+from packets import (insert_checksum, ipv4_udp, ipv6_udp, pack, random_packets, rx_ring,
+                     slot_ring)
+from test_gpu_tx import assert_same_bytes
 from warpcore_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -1313,6 +1317,115 @@ def test_host_path_unordered_gather(gpu, kind):
     got = wc.cksum_host(buf, offs, lens, kind=kind)
     np.testing.assert_array_equal(
         got, c_oracle.cksum_ragged(buf, offs, lens, kind=0 if kind == "ip" else 1))
+
+
+HANDOVER_N = 3100
+# The launch path each knob set forces for 3100 registered scrambled slots:
+# one zero-copy launch (<= 4096 packets, under 8 MiB); the in-place stream in
+# launches of 1024, 1024, 1024 and 52 packets (1024 is the floor of
+# WC_ZS_PKTS), so both buffers are used twice and the last chunk is partial;
+# the pipeline's packet-by-packet gather (scrambled slots do not ascend).
+HANDOVER_KNOBS = {"zero_copy": {},
+                  "stream": {"WC_ZC_BYTES": "0", "WC_ZS_PKTS": "1024"},
+                  "gather": {"WC_ZC_BYTES": "0", "WC_ZC_STREAM": "0"}}
+
+
+@pytest.fixture(params=list(HANDOVER_KNOBS))
+def handover_path(request, monkeypatch, gpu):
+    knobs = HANDOVER_KNOBS[request.param]
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    wc.reload_config()
+    yield request.param
+    for k in knobs:
+        monkeypatch.delenv(k)
+    wc.reload_config()
+
+
+@functools.lru_cache(maxsize=None)
+def handover_batch(what: str):
+    """(buf, offs, lens, want) of 3100 packets or frames in scrambled 2048-B
+    slots, with the oracle's results; shared by the runs and never written."""
+    n, slot = HANDOVER_N, 2048
+    rng = np.random.default_rng(n + len(what))
+    if what == "packets":
+        buf = rng.integers(0, 256, n * slot + 64, dtype=np.uint8)
+        pkts = random_packets(rng, n, max_payload=slot - 100, wild=True)
+        offs = (rng.permutation(n) * slot + rng.integers(0, 16, n)).astype(np.uint64)
+        lens = np.array([ln for _, ln in pkts], dtype=np.uint16)
+        for o, (p, _) in zip(offs, pkts):
+            buf[int(o): int(o) + len(p)] = np.frombuffer(p, dtype=np.uint8)
+        want = {"ip": c_oracle.cksum_ragged(buf, offs, lens, kind=0),
+                "payload": c_oracle.cksum_ragged(buf, offs, lens, kind=1),
+                "fused": fused_want(buf, offs, lens)}
+    else:
+        buf, offs, lens = slot_ring(rx_ring(rng, n), rng=rng)
+        if what == "tx":
+            tx_model.garble_fields(buf, offs, lens, rng)
+            want = tx_model.Expect(buf, offs, lens)
+        else:
+            want = c_oracle.rx_verdict_ragged(buf, offs, lens)
+    for a in (buf, offs, lens):
+        a.setflags(write=False)
+    return buf, offs, lens, want
+
+
+@pytest.mark.parametrize("call", ["ip", "payload", "fused", "rx", "tx"])
+def test_host_every_kind_every_path(gpu, call, handover_path):
+    """Every host call through every launch path, the hand-over between the
+    path's buffers crossed: each result array the call returns equals the
+    oracle's element for element (the seal: status codes, error count and the
+    frame bytes), and the resident server is never asked (n > 256)."""
+    what = {"rx": "rx", "tx": "tx"}.get(call, "packets")
+    shared, offs, lens, want = handover_batch(what)
+    buf = shared.copy()
+    wc.host_register(buf)
+    s0 = wc.server_stats()
+    try:
+        if call in ("ip", "payload"):
+            got = [wc.cksum_host(buf, offs, lens, kind=call)]
+            want = [want[call]]
+        elif call == "fused":
+            got, want = wc.cksum_ip_udp_host(buf, offs, lens), want["fused"]
+        elif call == "rx":
+            got = wc.rx_verdict_host(buf, offs, lens)
+            want = (want, int(np.isin(want, wc.RX_DROPS).sum()))
+        else:
+            got, want = wc.tx_seal_host(buf, offs, lens), (want.status, want.errors, want.buf)
+    finally:
+        wc.host_unregister(buf)
+    assert wc.server_stats() == s0
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(g, w)
+    if call == "tx":
+        assert_same_bytes(buf, want[2], f"host seal, {handover_path}")
+    else:
+        assert_same_bytes(buf, shared, f"{call} must not write the packets")
+
+
+def test_host_fused_pipeline_slot_reuse(gpu):
+    """3 * 2^20 + 64 minimal IPv4/UDP packets (28 bytes: IHL 5, an 8-byte UDP
+    header, no payload) back to back in pageable memory: the pipeline's range
+    copy in four chunks of at most 2^20 packets, the fourth in slot 0 again
+    with both result arrays in play.  (hl == len - 8: len >= hl, inside
+    payload_cksum's defined inputs.)"""
+    n = 3 * 2**20 + 64
+    rng = np.random.default_rng(28)
+    pk = rng.integers(0, 256, (n, 28), dtype=np.uint8)  # tos, id, ttl, addresses, ports: random
+    pk[:, 0] = 0x45
+    pk[:, 2:4] = (0, 28)        # total length
+    pk[:, 6:8] = (0x40, 0)      # DF
+    pk[:, 9] = 17
+    pk[:, 10:12] = 0            # header checksum
+    pk[:, 24:26] = (0, 8)       # UDP length
+    pk[:, 26:28] = 0            # UDP checksum
+    buf = pk.reshape(-1)
+    offs = np.arange(n, dtype=np.uint64) * 28
+    lens = np.full(n, 28, dtype=np.uint16)
+    want_h, want_p = fused_want(buf, offs, lens)
+    got_h, got_p = wc.cksum_ip_udp_host(buf, offs, lens)
+    np.testing.assert_array_equal(got_h, want_h)
+    np.testing.assert_array_equal(got_p, want_p)
 
 
 def test_host_path_rejects_out_of_range(gpu):

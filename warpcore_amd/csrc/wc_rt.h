@@ -47,7 +47,7 @@ constexpr int kKindFused = 3;
 // resident server's.
 constexpr int kKindTx = 4;
 constexpr int kKindTxZero = 5;
-inline bool kind_is_tx(int kind) { return kind == kKindTx || kind == kKindTxZero; }
+constexpr bool kind_is_tx(int kind) { return kind == kKindTx || kind == kKindTxZero; }
 
 // Small batches over registered memory skip the copy engines: the kernel
 // reads the packets straight out of the page-locked region over PCIe, and
@@ -59,31 +59,78 @@ constexpr int kZcBytesDefault = 8 << 20;
 // Measured on MI355X, tools/host_latency.py.
 constexpr uint64_t kZcGroupMax = 1024;
 
+// Result arrays of a host batch, per kind: the element width in bytes of up
+// to kOuts arrays, 0 = unused.  [0] the main results (a checksum, a 1-byte RX
+// verdict, the seal pass's udp->cksum values), [1] the IPv4 header checksums
+// of the fused pair and the seal pass, [2] the seal pass's status codes.
+// Every copy of results, and the check of the caller's pointers, walks this.
+constexpr int kOuts = 3;
+struct OutRow {
+    uint8_t w[kOuts];
+    constexpr bool is(int a, int b, int c) const { return w[0] == a && w[1] == b && w[2] == c; }
+};
+constexpr OutRow out_row(int kind)
+{
+    return kind == kKindRx      ? OutRow{{1, 0, 0}}
+           : kind == kKindFused ? OutRow{{2, 2, 0}}
+           : kind_is_tx(kind)   ? OutRow{{2, 2, 1}}
+                                : OutRow{{2, 0, 0}};
+}
+static_assert(out_row(WC_CKSUM_IP).is(2, 0, 0) && out_row(WC_CKSUM_PAYLOAD).is(2, 0, 0), "");
+static_assert(out_row(kKindRx).is(1, 0, 0) && out_row(kKindFused).is(2, 2, 0), "");
+static_assert(out_row(kKindTx).is(2, 2, 1) && out_row(kKindTxZero).is(2, 2, 1), "");
+constexpr OutRow kOutCap = out_row(kKindTx); // the widest row: what a buffer set holds
+
+// The caller's result arrays of a host batch, in out_row's order.
+struct HostOuts {
+    uint8_t *p[kOuts];
+};
+
+// The per-batch arrays of one launch: offsets, lengths and the result arrays,
+// as the host (h) and the device (d) address them.  Mapped: pinned host
+// memory the kernel reads and writes in place; staged: device memory plus
+// pinned host memory the pipeline copies between.
+struct BufView {
+    uint64_t *off = nullptr;
+    uint16_t *len = nullptr;
+    uint8_t *out[kOuts] = {};
+};
+struct BufSet {
+    BufView h, d;
+    bool mapped = false;
+    int alloc(uint64_t pkts, bool mapped_pinned);
+    void free(); // (safe on a partly built set)
+    // Packets [0, n)'s results of `kind` to the caller's arrays at packet lo.
+    void copy_out(int kind, const HostOuts &outs, uint64_t lo, uint64_t n) const;
+};
+
+// One launch in flight on a buffer set: the event recorded behind it and the
+// caller's packets [lo, lo + n) whose results it holds while `pend`.  A call
+// leaves none pending (host_zc_stream, PipeRun::fail).
+struct Slot {
+    hipEvent_t done = nullptr;
+    BufSet b;
+    bool pend = false;
+    uint64_t lo = 0, n = 0;
+    int init(uint64_t pkts, bool mapped_pinned);
+    void free();
+    void mark(uint64_t lo_, uint64_t n_) { pend = true, lo = lo_, n = n_; }
+    // Wait for the launch, if one is pending, and copy its results out.
+    int drain(int kind, const HostOuts &outs);
+};
+
+struct PipeSlot : Slot {
+    hipStream_t st = nullptr;
+    uint8_t *d_bytes = nullptr, *h_bytes = nullptr; // (h: pinned staging for unregistered input)
+};
 struct HostPipe {
-    hipStream_t st[kPipe] = {};
-    hipEvent_t done[kPipe] = {};
-    uint8_t *d_bytes[kPipe] = {};
-    uint64_t *d_off[kPipe] = {};
-    uint16_t *d_len[kPipe] = {};
-    uint16_t *d_out[kPipe] = {};
-    uint16_t *d_out2[kPipe] = {};  // fused pass: the IPv4 header checksums
-    uint8_t *d_st[kPipe] = {};     // TX seal pass: the status codes
-    uint8_t *h_bytes[kPipe] = {};  // pinned staging for unregistered input
-    uint64_t *h_off[kPipe] = {};   // pinned, rebased offsets
-    uint16_t *h_len[kPipe] = {};
-    uint16_t *h_out[kPipe] = {};
-    uint16_t *h_out2[kPipe] = {};
-    uint8_t *h_st[kPipe] = {};
+    PipeSlot slot[kPipe];
     bool ready = false;
 };
 
 struct ZeroCopy {
     hipStream_t st = nullptr;
-    uint64_t *h_off = nullptr, *d_off = nullptr; // mapped pinned
-    uint16_t *h_len = nullptr, *d_len = nullptr;
-    uint16_t *h_out = nullptr, *d_out = nullptr;
-    uint16_t *h_out2 = nullptr, *d_out2 = nullptr; // fused pass: header checksums
-    uint8_t *h_st = nullptr, *d_st = nullptr;      // TX seal pass: status codes
+    BufSet b; // mapped pinned
     bool ready = false;
 };
 
@@ -95,12 +142,7 @@ struct ZeroCopy {
 constexpr uint64_t kZsPkts = 1ull << 16;
 struct ZcStream {
     hipStream_t st = nullptr;
-    hipEvent_t done[2] = {};
-    uint64_t *h_off[2] = {}, *d_off[2] = {}; // mapped pinned
-    uint16_t *h_len[2] = {}, *d_len[2] = {};
-    uint16_t *h_out[2] = {}, *d_out[2] = {};
-    uint16_t *h_out2[2] = {}, *d_out2[2] = {}; // fused pass: header checksums
-    uint8_t *h_st[2] = {}, *d_st[2] = {};      // TX seal pass: status codes
+    Slot slot[2]; // mapped pinned
     bool ready = false;
 };
 
@@ -327,29 +369,25 @@ constexpr int kSrvFallback = 1; // serve_batch: not served, take the launch path
 // One small registered batch through the server (caller holds g_mu, the
 // device is current).  Returns kSrvFallback when the server can't take it.
 int serve_batch(Device &D, int dev, const uint8_t *dbase, const uint64_t *h_off,
-                const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                uint16_t *h_out2 = nullptr);
+                const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind);
 void server_stop_all_locked();
 // Whether small registered batches may go to the server (not paused).
 bool server_enabled_locked();
 
 // --- wc_rt_host.cpp -----------------------------------------------------------
 void pipe_free(HostPipe &P);
+void zc_free(ZeroCopy &Z);
 void zs_free(ZcStream &S);
 int pipe_init_locked(HostPipe &P);
 const uint8_t *registered_dptr_locked(const void *p, uint64_t bytes);
 uint64_t span_of(uint16_t len, int kind);
-int out_size(int kind);
 int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
-                   const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                   uint16_t *h_out2 = nullptr, uint8_t *h_st = nullptr);
+                   const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind);
 // A host-memory batch on the current device by the rules of wc_cksum_host
-// (server, zero-copy launch, zero-copy stream or pipeline).  h_out2: the
-// fused pair's and the TX seal pass's header checksums; h_st: the TX seal
-// pass's status codes.
+// (server, zero-copy launch, zero-copy stream or pipeline); outs: every
+// array out_row(kind) uses.
 int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
-               const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-               uint16_t *h_out2 = nullptr, uint8_t *h_st = nullptr);
+               const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind);
 // Every packet of a host batch inside [0, h_bytes); whether the offsets
 // ascend, the bytes the packets' checks read, and (optional) the byte range
 // they span.
@@ -358,29 +396,28 @@ bool host_batch_ok(const uint8_t *hb, uint64_t h_bytes, const uint64_t *h_off,
                    uint64_t *range = nullptr);
 void shard_range(uint64_t n, int g, int G, uint64_t *lo, uint64_t *hi);
 
-// Pipelined path over one HostPipe on one device (wc_rt_host.cpp): one chunk
-// per step(), so a single host thread can interleave the runs of several
-// devices (wc_cksum_host_multi).
-struct PipeRun {
-    Device *D = nullptr;
-    HostPipe *P = nullptr;
-    int dev = 0;
+// A checked host batch as the pipeline sees it.
+struct HostBatch {
     const uint8_t *hb = nullptr;
     bool registered = false, ascending = true;
     const uint64_t *h_off = nullptr;
     const uint16_t *h_len = nullptr;
-    uint8_t *h_out = nullptr; // out_size(kind) bytes per packet
-    uint16_t *h_out2 = nullptr; // fused pair: the header checksums
-    uint8_t *h_st = nullptr;    // TX seal pass: the status codes
     int kind = WC_CKSUM_IP;
+    HostOuts outs{};
+};
+
+// Pipelined path over one HostPipe on one device (wc_rt_host.cpp): packets
+// [i, hi) of a batch, one chunk per step(), so a single host thread can
+// interleave the runs of several devices (wc_cksum_host_multi).
+struct PipeRun : HostBatch {
+    Device *D = nullptr;
+    HostPipe *P = nullptr;
+    int dev = 0;
     uint64_t i = 0, hi = 0;
-    uint64_t pend_lo[kPipe] = {}, pend_n[kPipe] = {};
-    bool pend[kPipe] = {};
     int slot = 0;
 
     bool done() const { return i >= hi; }
     uint64_t span(uint64_t j) const;
-    int drain(int s);
     int fail(int rc);
     int step();
     int finish();

@@ -248,15 +248,7 @@ int wc_gpu_fini(void)
             continue;
         (void)hipSetDevice(d);
         pipe_free(D.pipe);
-        if (D.zc.ready) {
-            (void)hipStreamSynchronize(D.zc.st);
-            (void)hipStreamDestroy(D.zc.st);
-            (void)hipHostFree(D.zc.h_off);
-            (void)hipHostFree(D.zc.h_len);
-            (void)hipHostFree(D.zc.h_out);
-            (void)hipHostFree(D.zc.h_out2);
-            (void)hipHostFree(D.zc.h_st);
-        }
+        zc_free(D.zc);
         zs_free(D.zs);
         if (D.srv.ready) {
             (void)hipStreamDestroy(D.srv.st);

@@ -1,7 +1,10 @@
 // wc_rt_host.cpp -- host-memory batches (wc_cksum_host, wc_cksum_ip_udp_host,
-// wc_rx_verdict_host, wc_host_register): the resident server or one
-// zero-copy launch for a small registered batch, else the pipelined path
-// (hipMemcpyAsync H2D, kernel, D2H) through pinned staging.
+// wc_rx_verdict_host, the seal's compute pass, wc_host_register): the
+// resident server or one zero-copy launch for a small registered batch, else
+// the in-place stream or the pipelined path (hipMemcpyAsync H2D, kernel, D2H)
+// through pinned staging.  All three launch paths keep their per-batch arrays
+// in a BufSet (one alloc, free and copy_out), the chunked two in a Slot (one
+// drain), and pick a kind's result arrays from out_row (wc_rt.h).
 
 #include "wc_rt.h"
 
@@ -17,30 +20,95 @@ namespace wc {
 namespace rt __attribute__((visibility("hidden"))) {
 
 // ---------------------------------------------------------------------------
+// The per-batch arrays (BufSet) and the launch in flight on them (Slot).
+
+// One array of a set, in the set's flavour, on the current device.
+template <class T>
+static bool buf_alloc(bool mapped, T *&h, T *&d, uint64_t bytes)
+{
+    const unsigned fl = mapped ? hipHostMallocMapped | hipHostMallocCoherent : 0;
+    if (hipHostMalloc((void **)&h, bytes, fl) != hipSuccess)
+        return false;
+    return (mapped ? hipHostGetDevicePointer((void **)&d, h, 0)
+                   : hipMalloc((void **)&d, bytes)) == hipSuccess;
+}
+
+int BufSet::alloc(uint64_t pkts, bool mapped_pinned)
+{
+    mapped = mapped_pinned;
+    bool ok = buf_alloc(mapped, h.off, d.off, pkts * 8);
+    ok = ok && buf_alloc(mapped, h.len, d.len, pkts * 2);
+    for (int k = 0; k < kOuts && ok; ++k)
+        ok = buf_alloc(mapped, h.out[k], d.out[k], pkts * kOutCap.w[k]);
+    if (!ok)
+        free();
+    return ok ? WC_OK : WC_ENOMEM;
+}
+
+void BufSet::free()
+{
+    if (!mapped) { // (a mapped set's device view is the host memory's own)
+        (void)hipFree(d.off);
+        (void)hipFree(d.len);
+        for (uint8_t *p : d.out)
+            (void)hipFree(p);
+    }
+    (void)hipHostFree(h.off);
+    (void)hipHostFree(h.len);
+    for (uint8_t *p : h.out)
+        (void)hipHostFree(p);
+    *this = BufSet{};
+}
+
+void BufSet::copy_out(int kind, const HostOuts &outs, uint64_t lo, uint64_t n) const
+{
+    const OutRow row = out_row(kind);
+    for (int k = 0; k < kOuts; ++k)
+        if (row.w[k])
+            memcpy(outs.p[k] + lo * row.w[k], (const void *)h.out[k], n * row.w[k]);
+}
+
+int Slot::init(uint64_t pkts, bool mapped_pinned)
+{
+    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess)
+        return WC_ENOMEM;
+    return b.alloc(pkts, mapped_pinned);
+}
+
+void Slot::free()
+{
+    if (done)
+        (void)hipEventDestroy(done);
+    b.free();
+    *this = Slot{};
+}
+
+int Slot::drain(int kind, const HostOuts &outs)
+{
+    if (!pend)
+        return WC_OK;
+    const int rc = hip_err(hipEventSynchronize(done));
+    if (rc)
+        return rc;
+    b.copy_out(kind, outs, lo, n);
+    pend = false;
+    return WC_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Host-memory pipeline.
 
 // Frees whatever a (possibly partly built) pipeline holds.
 void pipe_free(HostPipe &P)
 {
-    for (int s = 0; s < kPipe; ++s) {
-        if (P.st[s])
-            (void)hipStreamSynchronize(P.st[s]);
-        (void)hipFree(P.d_bytes[s]);
-        (void)hipFree(P.d_off[s]);
-        (void)hipFree(P.d_len[s]);
-        (void)hipFree(P.d_out[s]);
-        (void)hipFree(P.d_out2[s]);
-        (void)hipFree(P.d_st[s]);
-        (void)hipHostFree(P.h_bytes[s]);
-        (void)hipHostFree(P.h_off[s]);
-        (void)hipHostFree(P.h_len[s]);
-        (void)hipHostFree(P.h_out[s]);
-        (void)hipHostFree(P.h_out2[s]);
-        (void)hipHostFree(P.h_st[s]);
-        if (P.done[s])
-            (void)hipEventDestroy(P.done[s]);
-        if (P.st[s])
-            (void)hipStreamDestroy(P.st[s]);
+    for (PipeSlot &s : P.slot) {
+        if (s.st)
+            (void)hipStreamSynchronize(s.st);
+        (void)hipFree(s.d_bytes);
+        (void)hipHostFree(s.h_bytes);
+        s.free();
+        if (s.st)
+            (void)hipStreamDestroy(s.st);
     }
     P = HostPipe{};
 }
@@ -51,21 +119,11 @@ int pipe_init_locked(HostPipe &P)
 {
     if (P.ready)
         return WC_OK;
-    for (int s = 0; s < kPipe; ++s) {
-        if (hipStreamCreateWithFlags(&P.st[s], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&P.done[s], hipEventDisableTiming) != hipSuccess ||
-            hipMalloc((void **)&P.d_bytes[s], kChunkBytes + 64) != hipSuccess ||
-            hipMalloc((void **)&P.d_off[s], kChunkPkts * 8) != hipSuccess ||
-            hipMalloc((void **)&P.d_len[s], kChunkPkts * 2) != hipSuccess ||
-            hipMalloc((void **)&P.d_out[s], kChunkPkts * 2) != hipSuccess ||
-            hipMalloc((void **)&P.d_out2[s], kChunkPkts * 2) != hipSuccess ||
-            hipMalloc((void **)&P.d_st[s], kChunkPkts) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_bytes[s], kChunkBytes + 64, 0) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_off[s], kChunkPkts * 8, 0) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_len[s], kChunkPkts * 2, 0) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_out[s], kChunkPkts * 2, 0) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_out2[s], kChunkPkts * 2, 0) != hipSuccess ||
-            hipHostMalloc((void **)&P.h_st[s], kChunkPkts, 0) != hipSuccess) {
+    for (PipeSlot &s : P.slot) {
+        if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess ||
+            hipMalloc((void **)&s.d_bytes, kChunkBytes + 64) != hipSuccess ||
+            hipHostMalloc((void **)&s.h_bytes, kChunkBytes + 64, 0) != hipSuccess ||
+            s.init(kChunkPkts, false) != WC_OK) {
             pipe_free(P);
             return WC_ENOMEM;
         }
@@ -74,24 +132,26 @@ int pipe_init_locked(HostPipe &P)
     return WC_OK;
 }
 
+void zc_free(ZeroCopy &Z)
+{
+    if (Z.st) {
+        (void)hipStreamSynchronize(Z.st);
+        (void)hipStreamDestroy(Z.st);
+    }
+    Z.b.free();
+    Z = ZeroCopy{};
+}
+
 int zc_init_locked(Device &D)
 {
     ZeroCopy &Z = D.zc;
     if (Z.ready)
         return WC_OK;
-    const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
     if (hipStreamCreateWithFlags(&Z.st, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void **)&Z.h_off, kZcPkts * 8, fl) != hipSuccess ||
-        hipHostMalloc((void **)&Z.h_len, kZcPkts * 2, fl) != hipSuccess ||
-        hipHostMalloc((void **)&Z.h_out, kZcPkts * 2, fl) != hipSuccess ||
-        hipHostMalloc((void **)&Z.h_out2, kZcPkts * 2, fl) != hipSuccess ||
-        hipHostMalloc((void **)&Z.h_st, kZcPkts, fl) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&Z.d_off, Z.h_off, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&Z.d_len, Z.h_len, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&Z.d_out, Z.h_out, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&Z.d_out2, Z.h_out2, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&Z.d_st, Z.h_st, 0) != hipSuccess)
+        Z.b.alloc(kZcPkts, true) != WC_OK) {
+        zc_free(Z);
         return WC_ENOMEM;
+    }
     Z.ready = true;
     return WC_OK;
 }
@@ -142,57 +202,56 @@ uint64_t fused_span(const uint8_t *p, uint16_t len)
     return (p[0] >> 4) == 4 ? std::max<uint64_t>(s, (uint64_t)(p[0] & 15u) * 4u) : s;
 }
 
-// Result bytes per packet in the main result array: a uint16 checksum, or a
-// uint8 RX verdict.
-int out_size(int kind) { return kind == kKindRx ? 1 : 2; }
-
 // One device launch over a ragged batch of `kind` (a checksum kind, RX
-// verdicts -- lengths are frame lengths --, or the fused pair, whose header
-// checksums go to d_out_hdr).
-int run_ragged_any(Device &D, const Config &C, const uint8_t *d_base, const uint64_t *d_off,
-                   const uint16_t *d_len, uint64_t n, void *d_out, int kind, bool zero_copy,
-                   hipStream_t st, uint16_t *d_out_hdr = nullptr, uint8_t *d_st = nullptr)
+// verdicts -- lengths are frame lengths --, the fused pair or the seal's
+// compute pass): offsets, lengths and result arrays are b's device view.
+int run_ragged_any(Device &D, const Config &C, const uint8_t *d_base, const BufView &b,
+                   uint64_t n, int kind, bool zero_copy, hipStream_t st)
 {
+    uint16_t *const d_out = (uint16_t *)b.out[0], *const d_out_hdr = (uint16_t *)b.out[1];
     if (kind == kKindRx)
-        return hip_err(rx_launch(D, C, d_base, d_off, d_len, n, (uint8_t *)d_out, nullptr, st));
+        return hip_err(rx_launch(D, C, d_base, b.off, b.len, n, b.out[0], nullptr, st));
     if (kind_is_tx(kind)) // compute only: the calling thread makes the stores (wc_rt_tx.cpp)
         return hip_err(wc::launch_tx_seal(
-            const_cast<uint8_t *>(d_base), d_off, d_len, n,
-            wc::kTxNoStore | (kind == kKindTxZero ? wc::kTxZeroUdp : 0u), d_st, d_out_hdr,
-            (uint16_t *)d_out, nullptr, C.nt != 0, st));
+            const_cast<uint8_t *>(d_base), b.off, b.len, n,
+            wc::kTxNoStore | (kind == kKindTxZero ? wc::kTxZeroUdp : 0u), b.out[2], d_out_hdr,
+            d_out, nullptr, C.nt != 0, st));
     const bool fused = kind == kKindFused;
     const int k = fused ? WC_CKSUM_PAYLOAD : kind;
     const Plan p = plan_ragged(D, C, n, k, zero_copy, fused);
-    wc::LaunchArgs a{d_base, 0,       0,    d_off, d_len, n,
-                     (uint16_t *)d_out, nullptr, k, true,  false, C.nt != 0,
-                     C.flat_tpw, fused ? d_out_hdr : nullptr};
+    wc::LaunchArgs a{d_base, 0,       0, b.off, b.len, n,         d_out,
+                     nullptr, k,       true,  false, C.nt != 0, C.flat_tpw,
+                     fused ? d_out_hdr : nullptr};
     return run(D, C, a, p, st);
 }
 
 // Small registered batch: one launch reading host memory in place.
 int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
-                   const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                   uint16_t *h_out2, uint8_t *h_st)
+                   const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind)
 {
     int rc = zc_init_locked(D);
     if (rc)
         return rc;
     ZeroCopy &Z = D.zc;
-    memcpy(Z.h_off, h_off, n * 8);
-    memcpy(Z.h_len, h_len, n * 2);
-    rc = run_ragged_any(D, g_cfg, dbase, Z.d_off, Z.d_len, n, Z.d_out, kind, true, Z.st,
-                        Z.d_out2, Z.d_st);
-    if (rc)
-        return rc;
-    hipError_t e = hipStreamSynchronize(Z.st);
-    if (e != hipSuccess)
-        return hip_err(e);
-    memcpy(h_out, (const void *)Z.h_out, n * out_size(kind));
-    if (kind == kKindFused || kind_is_tx(kind))
-        memcpy(h_out2, (const void *)Z.h_out2, n * 2);
-    if (kind_is_tx(kind))
-        memcpy(h_st, (const void *)Z.h_st, n);
-    return WC_OK;
+    memcpy(Z.b.h.off, h_off, n * 8);
+    memcpy(Z.b.h.len, h_len, n * 2);
+    rc = run_ragged_any(D, g_cfg, dbase, Z.b.d, n, kind, true, Z.st);
+    if (rc == WC_OK)
+        rc = hip_err(hipStreamSynchronize(Z.st));
+    if (rc == WC_OK)
+        Z.b.copy_out(kind, outs, 0, n);
+    return rc;
+}
+
+void zs_free(ZcStream &S)
+{
+    if (S.st)
+        (void)hipStreamSynchronize(S.st);
+    for (Slot &s : S.slot)
+        s.free();
+    if (S.st)
+        (void)hipStreamDestroy(S.st);
+    S = ZcStream{};
 }
 
 int zs_init_locked(Device &D)
@@ -200,21 +259,8 @@ int zs_init_locked(Device &D)
     ZcStream &S = D.zs;
     if (S.ready)
         return WC_OK;
-    const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
-    bool ok = hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking) == hipSuccess;
-    for (int b = 0; b < 2 && ok; ++b)
-        ok = hipEventCreateWithFlags(&S.done[b], hipEventDisableTiming) == hipSuccess &&
-             hipHostMalloc((void **)&S.h_off[b], kZsPkts * 8, fl) == hipSuccess &&
-             hipHostMalloc((void **)&S.h_len[b], kZsPkts * 2, fl) == hipSuccess &&
-             hipHostMalloc((void **)&S.h_out[b], kZsPkts * 2, fl) == hipSuccess &&
-             hipHostMalloc((void **)&S.h_out2[b], kZsPkts * 2, fl) == hipSuccess &&
-             hipHostMalloc((void **)&S.h_st[b], kZsPkts, fl) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&S.d_off[b], S.h_off[b], 0) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&S.d_len[b], S.h_len[b], 0) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&S.d_out[b], S.h_out[b], 0) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&S.d_out2[b], S.h_out2[b], 0) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&S.d_st[b], S.h_st[b], 0) == hipSuccess;
-    if (!ok) {
+    if (hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking) != hipSuccess ||
+        S.slot[0].init(kZsPkts, true) != WC_OK || S.slot[1].init(kZsPkts, true) != WC_OK) {
         zs_free(S);
         return WC_ENOMEM;
     }
@@ -222,77 +268,40 @@ int zs_init_locked(Device &D)
     return WC_OK;
 }
 
-void zs_free(ZcStream &S)
-{
-    if (S.st)
-        (void)hipStreamSynchronize(S.st);
-    for (int b = 0; b < 2; ++b) {
-        if (S.done[b])
-            (void)hipEventDestroy(S.done[b]);
-        (void)hipHostFree(S.h_off[b]);
-        (void)hipHostFree(S.h_len[b]);
-        (void)hipHostFree(S.h_out[b]);
-        (void)hipHostFree(S.h_out2[b]);
-        (void)hipHostFree(S.h_st[b]);
-    }
-    if (S.st)
-        (void)hipStreamDestroy(S.st);
-    S = ZcStream{};
-}
-
 // A large batch in a registered region (ZcStream): chunk k's launch reads
 // its packets in place while the host writes chunk k + 1's offsets and
 // lengths into the other buffer and copies chunk k - 1's results out.
 int host_zc_stream(Device &D, const uint8_t *dbase, const uint64_t *h_off,
-                   const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                   uint16_t *h_out2, uint8_t *h_st)
+                   const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind)
 {
     int rc = zs_init_locked(D);
     if (rc)
         return rc;
     ZcStream &S = D.zs;
-    const int osz = out_size(kind);
-    uint64_t pend_lo[2] = {}, pend_n[2] = {};
-    bool pend[2] = {};
-    auto drain = [&](int b) -> int {
-        if (!pend[b])
-            return WC_OK;
-        const hipError_t e = hipEventSynchronize(S.done[b]);
-        if (e != hipSuccess)
-            return hip_err(e);
-        memcpy(h_out + pend_lo[b] * osz, (const void *)S.h_out[b], pend_n[b] * osz);
-        if (kind == kKindFused || kind_is_tx(kind))
-            memcpy(h_out2 + pend_lo[b], (const void *)S.h_out2[b], pend_n[b] * 2);
-        if (kind_is_tx(kind))
-            memcpy(h_st + pend_lo[b], (const void *)S.h_st[b], pend_n[b]);
-        pend[b] = false;
-        return WC_OK;
-    };
     int b = 0;
     const uint64_t per = g_cfg.zs_pkts;
     for (uint64_t i = 0; i < n && rc == WC_OK; i += per, b ^= 1) {
+        Slot &s = S.slot[b];
         const uint64_t cnt = std::min(per, n - i);
-        rc = drain(b); // (chunk k - 2's results: its buffers are free again)
+        rc = s.drain(kind, outs); // (chunk k - 2's results: its buffers are free again)
         if (rc)
             break;
-        memcpy(S.h_off[b], h_off + i, cnt * 8);
-        memcpy(S.h_len[b], h_len + i, cnt * 2);
-        rc = run_ragged_any(D, g_cfg, dbase, S.d_off[b], S.d_len[b], cnt, S.d_out[b], kind, true,
-                            S.st, S.d_out2[b], S.d_st[b]);
+        memcpy(s.b.h.off, h_off + i, cnt * 8);
+        memcpy(s.b.h.len, h_len + i, cnt * 2);
+        rc = run_ragged_any(D, g_cfg, dbase, s.b.d, cnt, kind, true, S.st);
         if (rc == WC_OK)
-            rc = hip_err(hipEventRecord(S.done[b], S.st));
-        if (rc == WC_OK) {
-            pend[b] = true;
-            pend_lo[b] = i;
-            pend_n[b] = cnt;
-        }
+            rc = hip_err(hipEventRecord(s.done, S.st));
+        if (rc == WC_OK)
+            s.mark(i, cnt);
     }
     if (rc == WC_OK)
-        rc = drain(b); // the older of the two in flight first
+        rc = S.slot[b].drain(kind, outs); // the older of the two in flight first
     if (rc == WC_OK)
-        rc = drain(b ^ 1);
-    if (rc != WC_OK) // (nothing may still write the mapped buffers the next call refills)
+        rc = S.slot[b ^ 1].drain(kind, outs);
+    if (rc != WC_OK) { // (nothing may still write the mapped buffers the next call refills)
         (void)hipStreamSynchronize(S.st);
+        S.slot[0].pend = S.slot[1].pend = false;
+    }
     return rc;
 }
 
@@ -424,32 +433,14 @@ uint64_t PipeRun::span(uint64_t j) const
     return kind == kKindFused ? fused_span(hb + h_off[j], h_len[j]) : span_of(h_len[j], kind);
 }
 
-// Wait for a slot's chunk and copy its results out.
-int PipeRun::drain(int s)
-{
-    if (!pend[s])
-        return WC_OK;
-    hipError_t e = hipEventSynchronize(P->done[s]);
-    if (e != hipSuccess)
-        return hip_err(e);
-    const int osz = out_size(kind);
-    memcpy(h_out + pend_lo[s] * osz, P->h_out[s], pend_n[s] * osz);
-    if (kind == kKindFused || kind_is_tx(kind))
-        memcpy(h_out2 + pend_lo[s], P->h_out2[s], pend_n[s] * 2);
-    if (kind_is_tx(kind))
-        memcpy(h_st + pend_lo[s], P->h_st[s], pend_n[s]);
-    pend[s] = false;
-    return WC_OK;
-}
-
 // On any error, wait for every slot's in-flight copies and kernel before
 // returning: they use the library's pinned staging, which the next call
 // rewrites with plain memcpy.
 int PipeRun::fail(int rc)
 {
-    for (int s = 0; s < kPipe; ++s) {
-        (void)hipStreamSynchronize(P->st[s]);
-        pend[s] = false;
+    for (PipeSlot &s : P->slot) {
+        (void)hipStreamSynchronize(s.st);
+        s.pend = false;
     }
     return rc;
 }
@@ -457,9 +448,11 @@ int PipeRun::fail(int rc)
 // Stage and enqueue the next chunk (caller: current device = dev).
 int PipeRun::step()
 {
-    int rc = drain(slot);
+    PipeSlot &S = P->slot[slot];
+    int rc = S.drain(kind, outs);
     if (rc)
         return rc;
+    const BufView &sh = S.b.h, &sd = S.b.d;
     const uint64_t i0 = i;
     uint64_t j = i, bytes = 0;
     const uint8_t *src = nullptr;
@@ -471,15 +464,15 @@ int PipeRun::step()
             if (std::max(top, e) - lo > kChunkBytes && j > i0)
                 break;
             top = std::max(top, e);
-            P->h_off[slot][j - i0] = h_off[j] - lo;
-            P->h_len[slot][j - i0] = h_len[j];
+            sh.off[j - i0] = h_off[j] - lo;
+            sh.len[j - i0] = h_len[j];
             ++j;
         }
         bytes = top - lo;
         src = hb + lo;
         if (!registered) {
-            stage_copy(P->h_bytes[slot], src, bytes);
-            src = P->h_bytes[slot];
+            stage_copy(S.h_bytes, src, bytes);
+            src = S.h_bytes;
         }
     } else {
         // Rebased offsets first (a prefix sum), then the packet copies
@@ -488,16 +481,16 @@ int PipeRun::step()
             const uint64_t sp = span(j);
             if (bytes + sp > kChunkBytes && j > i0)
                 break;
-            P->h_off[slot][j - i0] = bytes;
-            P->h_len[slot][j - i0] = h_len[j];
+            sh.off[j - i0] = bytes;
+            sh.len[j - i0] = h_len[j];
             bytes += sp;
             ++j;
         }
         const uint64_t cnt = j - i0;
         StagePool &pool = stage_pool();
         const int parts = (int)std::min<uint64_t>((uint64_t)pool.width(), (cnt + 4095) / 4096);
-        uint8_t *dst = P->h_bytes[slot];
-        const uint64_t *roff = P->h_off[slot];
+        uint8_t *dst = S.h_bytes;
+        const uint64_t *roff = sh.off;
         auto gather = [&](int t) {
             const uint64_t a = cnt * (uint64_t)t / (uint64_t)parts;
             const uint64_t b = cnt * (uint64_t)(t + 1) / (uint64_t)parts;
@@ -505,37 +498,29 @@ int PipeRun::step()
                 memcpy(dst + roff[q], hb + h_off[i0 + q], span(i0 + q));
         };
         pool.run(std::max(parts, 1), gather);
-        src = P->h_bytes[slot];
+        src = S.h_bytes;
     }
     const uint64_t cnt = j - i0;
-    hipStream_t st = P->st[slot];
-    hipError_t e = hipMemcpyAsync(P->d_bytes[slot], src, bytes, hipMemcpyHostToDevice, st);
+    hipStream_t st = S.st;
+    hipError_t e = hipMemcpyAsync(S.d_bytes, src, bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(P->d_off[slot], P->h_off[slot], cnt * 8, hipMemcpyHostToDevice,
-                           st);
+        e = hipMemcpyAsync(sd.off, sh.off, cnt * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(P->d_len[slot], P->h_len[slot], cnt * 2, hipMemcpyHostToDevice,
-                           st);
+        e = hipMemcpyAsync(sd.len, sh.len, cnt * 2, hipMemcpyHostToDevice, st);
     if (e != hipSuccess)
         return hip_err(e);
-    rc = run_ragged_any(*D, g_cfg, P->d_bytes[slot], P->d_off[slot], P->d_len[slot], cnt,
-                        P->d_out[slot], kind, false, st, P->d_out2[slot], P->d_st[slot]);
+    rc = run_ragged_any(*D, g_cfg, S.d_bytes, sd, cnt, kind, false, st);
     if (rc)
         return rc;
-    e = hipMemcpyAsync(P->h_out[slot], P->d_out[slot], cnt * out_size(kind),
-                       hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && (kind == kKindFused || kind_is_tx(kind)))
-        e = hipMemcpyAsync(P->h_out2[slot], P->d_out2[slot], cnt * 2, hipMemcpyDeviceToHost,
-                           st);
-    if (e == hipSuccess && kind_is_tx(kind))
-        e = hipMemcpyAsync(P->h_st[slot], P->d_st[slot], cnt, hipMemcpyDeviceToHost, st);
+    const OutRow row = out_row(kind);
+    for (int k = 0; k < kOuts && e == hipSuccess; ++k)
+        if (row.w[k])
+            e = hipMemcpyAsync(sh.out[k], sd.out[k], cnt * row.w[k], hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
-        e = hipEventRecord(P->done[slot], st);
+        e = hipEventRecord(S.done, st);
     if (e != hipSuccess)
         return hip_err(e);
-    pend[slot] = true;
-    pend_lo[slot] = i0;
-    pend_n[slot] = cnt;
+    S.mark(i0, cnt);
     i = j;
     slot = (slot + 1) % kPipe;
     return WC_OK;
@@ -544,7 +529,7 @@ int PipeRun::step()
 int PipeRun::finish()
 {
     for (int s = 0; s < kPipe; ++s) {
-        int rc = drain((slot + s) % kPipe);
+        int rc = P->slot[(slot + s) % kPipe].drain(kind, outs);
         if (rc)
             return rc;
     }
@@ -587,23 +572,9 @@ void shard_range(uint64_t n, int g, int G, uint64_t *lo, uint64_t *hi)
     *hi = (uint64_t)((unsigned __int128)n * (unsigned)(g + 1) / (unsigned)G);
 }
 
-int host_pipeline(Device &D, const uint8_t *hb, bool registered, bool ascending,
-                  const uint64_t *h_off, const uint16_t *h_len, uint64_t n,
-                  uint8_t *h_out, int kind, uint16_t *h_out2, uint8_t *h_st)
+int host_pipeline(Device &D, const HostBatch &b, uint64_t n)
 {
-    PipeRun r;
-    r.D = &D;
-    r.P = &D.pipe;
-    r.hb = hb;
-    r.registered = registered;
-    r.ascending = ascending;
-    r.h_off = h_off;
-    r.h_len = h_len;
-    r.h_out = h_out;
-    r.h_out2 = h_out2;
-    r.h_st = h_st;
-    r.kind = kind;
-    r.hi = n;
+    PipeRun r{b, &D, &D.pipe, 0, 0, n};
     while (!r.done()) {
         const int rc = r.step();
         if (rc)
@@ -613,20 +584,20 @@ int host_pipeline(Device &D, const uint8_t *hb, bool registered, bool ascending,
     return rc ? r.fail(rc) : WC_OK;
 }
 
-
-// wc_cksum_host / wc_rx_verdict_host / wc_cksum_ip_udp_host: a host-memory
-// batch on the current device -- the resident server or one zero-copy launch
-// for a small registered batch, else the pipeline.  h_out2: the fused pair's
-// header checksums.
+// wc_cksum_host / wc_rx_verdict_host / wc_cksum_ip_udp_host / the seal's
+// compute pass: a host-memory batch on the current device -- the resident
+// server or one zero-copy launch for a small registered batch, else the
+// in-place stream or the pipeline.
 int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
-               const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind, uint16_t *h_out2,
-               uint8_t *h_st)
+               const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind)
 {
     if (n == 0)
         return WC_OK;
-    if (!h_base || !h_off || !h_len || !h_out || (kind == kKindFused && !h_out2) ||
-        (kind_is_tx(kind) && (!h_out2 || !h_st)))
+    if (!h_base || !h_off || !h_len)
         return WC_EINVAL;
+    for (int k = 0; k < kOuts; ++k)
+        if (out_row(kind).w[k] && !outs.p[k])
+            return WC_EINVAL;
     bool ascending = true;
     uint64_t total = 0, range = 0;
     if (!host_batch_ok((const uint8_t *)h_base, h_bytes, h_off, h_len, n, kind, &ascending,
@@ -649,27 +620,27 @@ int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
             fits = span_of(h_len[i], kind) + (kind == kKindFused ? 40u : 0u) <= wc::kSrvMaxBytes;
         int dev = 0;
         if (fits && current_device(&dev) == WC_OK) {
-            rc = serve_batch(*D, dev, dbase, h_off, h_len, n, h_out, kind, h_out2);
+            rc = serve_batch(*D, dev, dbase, h_off, h_len, n, outs, kind);
             if (rc != kSrvFallback)
                 return rc;
         }
     }
     if (dbase && n <= kZcPkts && total <= (uint64_t)g_cfg.zc_bytes)
-        return host_zero_copy(*D, dbase, h_off, h_len, n, h_out, kind, h_out2, h_st);
+        return host_zero_copy(*D, dbase, h_off, h_len, n, outs, kind);
     // A large registered batch: sparse or in any order, the kernels read its
     // packets in place (only the lines they touch cross the link); dense and
     // ascending, the pipeline's range DMA is a little faster (C2 bytes from a
     // registered region: 54.5 vs 52.9 GB/s, the three sparse ring calls 39 ->
     // 46-47 GB/s: profiles/e2e_r06b.log).
     if (dbase && g_cfg.zc_stream && (sparse || !ascending))
-        return host_zc_stream(*D, dbase, h_off, h_len, n, h_out, kind, h_out2, h_st);
+        return host_zc_stream(*D, dbase, h_off, h_len, n, outs, kind);
     rc = pipe_init_locked(D->pipe);
     if (rc)
         return rc;
     // (pageable and sparse: gathered packet by packet into the staging, not
     // the whole range with its gaps)
-    return host_pipeline(*D, (const uint8_t *)h_base, dbase != nullptr, ascending && !sparse,
-                         h_off, h_len, n, h_out, kind, h_out2, h_st);
+    return host_pipeline(*D, {(const uint8_t *)h_base, dbase != nullptr, ascending && !sparse,
+                              h_off, h_len, kind, outs}, n);
 }
 
 } // namespace rt
@@ -751,7 +722,7 @@ int wc_cksum_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
 {
     if (kind != WC_CKSUM_IP && kind != WC_CKSUM_PAYLOAD)
         return WC_EINVAL;
-    return host_batch(h_base, h_bytes, h_off, h_len, n, (uint8_t *)h_out, kind);
+    return host_batch(h_base, h_bytes, h_off, h_len, n, {{(uint8_t *)h_out}}, kind);
 }
 
 int wc_cksum_ip_udp_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
@@ -760,8 +731,8 @@ int wc_cksum_ip_udp_host(const void *h_base, uint64_t h_bytes, const uint64_t *h
 {
     if (n && (!h_out_ip_hdr || !h_out_payload))
         return WC_EINVAL;
-    return host_batch(h_base, h_bytes, h_off, h_len, n, (uint8_t *)h_out_payload, kKindFused,
-                      h_out_ip_hdr);
+    return host_batch(h_base, h_bytes, h_off, h_len, n,
+                      {{(uint8_t *)h_out_payload, (uint8_t *)h_out_ip_hdr}}, kKindFused);
 }
 
 int wc_rx_verdict_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
@@ -770,7 +741,7 @@ int wc_rx_verdict_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
 {
     if (n && !h_verdict)
         return WC_EINVAL;
-    const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n, h_verdict, kKindRx);
+    const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n, {{h_verdict}}, kKindRx);
     if (rc == WC_OK && h_drops) {
         uint64_t d = 0;
         for (uint64_t i = 0; i < n; ++i)

@@ -143,6 +143,7 @@ int wc_cksum_host_multi(const void *h_base, uint64_t h_bytes, const uint64_t *h_
     if (!host_batch_ok((const uint8_t *)h_base, h_bytes, h_off, h_len, n, kind, &ascending,
                        &total))
         return WC_EINVAL;
+    const HostOuts outs{{(uint8_t *)h_out}};
     {
         std::lock_guard<FairMutex> lk(g_mu);
         G = g_multi_n;
@@ -159,24 +160,15 @@ int wc_cksum_host_multi(const void *h_base, uint64_t h_bytes, const uint64_t *h_
             if (rc == WC_OK && !dbase)
                 rc = WC_EINVAL;
             if (rc == WC_OK)
-                rc = host_zero_copy(*D, dbase, h_off, h_len, n, (uint8_t *)h_out, kind);
+                rc = host_zero_copy(*D, dbase, h_off, h_len, n, outs, kind);
             (void)hipSetDevice(cur);
             return rc;
         }
+        const HostBatch b{(const uint8_t *)h_base, registered, ascending, h_off, h_len, kind, outs};
         PipeRun runs[kMaxDevices];
         for (int g = 0; g < G; ++g) {
-            PipeRun &r = runs[g];
-            r.D = &g_dev[g_shard[g].dev];
-            r.P = &g_shard[g].pipe;
-            r.dev = g_shard[g].dev;
-            r.hb = (const uint8_t *)h_base;
-            r.registered = registered;
-            r.ascending = ascending;
-            r.h_off = h_off;
-            r.h_len = h_len;
-            r.h_out = (uint8_t *)h_out;
-            r.kind = kind;
-            shard_range(n, g, G, &r.i, &r.hi);
+            runs[g] = PipeRun{b, &g_dev[g_shard[g].dev], &g_shard[g].pipe, g_shard[g].dev};
+            shard_range(n, g, G, &runs[g].i, &runs[g].hi);
         }
         // One thread, G pipelines: each pass stages one chunk per unfinished
         // shard, so every device's copies and kernels overlap the staging of

@@ -177,11 +177,11 @@ void server_post(Server &S, uint32_t seq, const uint8_t *dbase, const uint64_t *
 
 // One small registered batch through the server (caller holds g_mu, the
 // device is current).  Returns kSrvFallback when the server can't take it.
-// h_out2: the fused pair's header checksums (kind kKindFused).
 int serve_batch(Device &D, int dev, const uint8_t *dbase, const uint64_t *h_off,
-                const uint16_t *h_len, uint64_t n, uint8_t *h_out, int kind,
-                uint16_t *h_out2)
+                const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind)
 {
+    uint8_t *const h_out = outs.p[0];
+    uint16_t *const h_out2 = (uint16_t *)outs.p[1]; // (kKindFused: the header checksums)
     Server &S = D.srv;
     if (S.broken) {
         ++g_srv_stats.fallbacks;

@@ -56,8 +56,9 @@ int wc_tx_seal_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off,
         return WC_ENOMEM;
     uint16_t *udp = vals, *iph = vals + n;
     const bool zero_udp = flags & WC_TX_ZERO_UDP_CKSUM;
-    const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n, (uint8_t *)udp,
-                              zero_udp ? kKindTxZero : kKindTx, iph, h_status);
+    const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n,
+                              {{(uint8_t *)udp, (uint8_t *)iph, h_status}},
+                              zero_udp ? kKindTxZero : kKindTx);
     if (rc == WC_OK) {
         // The stores of mk_ip4_hdr and udp_tx (ip4.c:184-186, udp.c:209-213),
         // by the status: a frame that has one is IPv4 or IPv6 with its header
