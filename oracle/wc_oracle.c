@@ -6,11 +6,14 @@
  * the HIP kernels and the timed CPU baseline; it is never linked into the
  * product library.
  *
- * Parity: "parity unpinned" against the reference except for the known
- * answers in tests/golden/kat.json (recorded by SURVEY.md/BASELINE.md from the
- * compiled reference object) -- the reference itself is unbuildable here
- * because in_cksum.c needs the CMake-generated <warpcore/config.h>.  The
- * standard arithmetic is also pinned by Linux-kernel-computed checksums
+ * Parity: ip_cksum and payload_cksum are pinned bit-exact to the reference's
+ * own in_cksum.c, compiled unchanged into oracle/_ref/libwc_ref.so (Makefile
+ * target `ref`), by tests/test_reference.py over the domain listed in
+ * DESIGN.md section 3 -- everything but payload_cksum with len < hl, where
+ * the reference has no behaviour.  The RX verdict chain below stays a
+ * restatement (ip4.c / ip6.c / udp.c / eth.c need netmap), checked against
+ * the reference at its two checksum decisions.  Also pinned by the known
+ * answers in tests/golden/kat.json and by Linux-kernel-computed checksums
  * (tests/golden/linux_vectors.npz).
  */
 #define _GNU_SOURCE

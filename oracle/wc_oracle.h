@@ -15,14 +15,16 @@
  *   /root/reference/lib/src/ip4.h:55-66,75-92   ip4_hdr layout, ip_v, ip4_hl
  *   /root/reference/lib/src/ip6.h:45-57         ip6_hdr layout
  *
- * Parity status: the reference object cannot be built here (in_cksum.c pulls
- * <warpcore/config.h>, which only CMake generates), so this restatement is
- * pinned only by the known answers SURVEY.md / BASELINE.md recorded from the
- * compiled reference (tests/golden/kat.json) and by external RFC examples.
- * Everything else is "parity unpinned" against the reference -- see DESIGN.md
- * section 3.  The standard RFC 1071 arithmetic (word sum, fold, byte order,
- * IPv4 / IPv6 pseudo-headers with next header 17) is additionally pinned by
- * checksums the Linux kernel computed on the same bytes
+ * Parity status: the two checksum functions are pinned bit-exact to the
+ * reference's own object (oracle/_ref/libwc_ref.so: in_cksum.c compiled
+ * unchanged after CMake generated its <warpcore/config.h>) by
+ * tests/test_reference.py -- see DESIGN.md section 3 for the domain; the RX
+ * verdict chain stays a restatement, checked at its two checksum decisions.
+ * Besides, the known answers SURVEY.md / BASELINE.md recorded from the
+ * compiled reference (tests/golden/kat.json) and external RFC examples, and
+ * the standard RFC 1071 arithmetic (word sum, fold, byte order,
+ * IPv4 / IPv6 pseudo-headers with next header 17) is pinned by checksums the
+ * Linux kernel computed on the same bytes
  * (tests/golden/linux_vectors.npz, make_kernel_vectors.py).
  */
 #pragma once

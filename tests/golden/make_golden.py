@@ -1,10 +1,12 @@
 """Regenerate tests/golden/vectors.npz (regression vectors).
 
 Expected values come from the independent pure-Python restatement
-(oracle/py_oracle.py), NOT from the reference (which cannot be built here --
-DESIGN.md section 3).  The file pins the C restatement, the GPU kernels and
-future edits to one spec; the reference-derived known answers live in
-kat.json.
+(oracle/py_oracle.py), not from the reference.  The file pins the C
+restatement, the GPU kernels and future edits to one spec.  What ties that
+spec to the reference is elsewhere: tests/test_reference.py compares both
+restatements with the reference's own in_cksum.c object, ref_vectors.npz
+(make_ref_vectors.py) holds results recorded from it, and kat.json the
+reference-derived known answers.
 
     python tests/golden/make_golden.py
 """

@@ -2,9 +2,10 @@
 kernel's own RFC 1071 code, an implementation independent of this project
 and of the reference.
 
-The reference (lib/src/in_cksum.c) cannot be built here, and its tests hold
-no checksum vectors.  These fixtures pin the oracle and
-the GPU kernels to an external implementation on the same bytes:
+The reference's tests hold no checksum vectors.  Its
+own object pins the oracle elsewhere (tests/test_reference.py); these fixtures
+pin the oracle and the GPU kernels to an external implementation on the same
+bytes:
 
 * ``icmp``  -- ICMP echo replies from the loopback host.  The kernel builds
   each reply (icmp_reply -> csum_partial / csum_fold) over the request's

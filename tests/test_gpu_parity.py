@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import refcases
 import tx_model
 import warpcore_amd as wc
 from oracle import c_oracle, py_oracle
@@ -98,6 +99,173 @@ def test_golden_vectors_payload(gpu):
     out = wc.cksum_ragged(dev_u8(g["pl_blob"], gpu), to_dev(g["pl_off"], gpu),
                           to_dev(g["pl_len"], gpu), kind="payload")
     np.testing.assert_array_equal(host(out), g["pl_expect"])
+
+
+# ---------------------------------------------------------------------------
+# Results recorded from the reference's own in_cksum.c (tests/golden/
+# ref_vectors.npz, make_ref_vectors.py): every entry point of the library
+# against what the reference computed, not against a restatement of it.  The
+# file's groups: ip (start phase x length), pl (wild and plain UDP packets,
+# the 65535-byte IPv6 next_hdr wrap, every version x IHL nibble), fu (the UDP
+# packets of pl: header checksum and payload_cksum), st (strided shapes,
+# bodies rebuilt by refcases.st_blob), tx (the seal's two stored values).
+
+@functools.lru_cache(maxsize=None)
+def ref_vectors():
+    g = dict(np.load(refcases.REF_VECTORS))
+    for k in range(len(refcases.ST_SHAPES)):
+        g[f"st{k}_blob"] = refcases.st_blob(g, k)
+    g["tx_buf"], g["tx_off"], g["tx_len"] = refcases.tx_frames(g)
+    return g  # shared by the tests below and never written
+
+
+@pytest.mark.parametrize("mode", list(RAGGED_MODES))
+@pytest.mark.parametrize("group,kind", [("ip", "ip"), ("pl", "payload")])
+def test_ref_vectors_ragged(gpu, monkeypatch, group, kind, mode):
+    ragged_mode(monkeypatch, mode)
+    g = ref_vectors()
+    out = wc.cksum_ragged(dev_u8(g[group + "_blob"], gpu), to_dev(g[group + "_off"], gpu),
+                          to_dev(g[group + "_len"], gpu), kind=kind)
+    np.testing.assert_array_equal(host(out), g[group + "_expect"])
+
+
+@pytest.mark.parametrize("kind", ["ip", "payload"])
+@pytest.mark.parametrize("k", range(len(refcases.ST_SHAPES)))
+def test_ref_vectors_strided(gpu, k, kind):
+    g = ref_vectors()
+    length, stride = refcases.ST_SHAPES[k]
+    out = wc.cksum_strided(dev_u8(g[f"st{k}_blob"], gpu, pad=0), stride, length, refcases.ST_N,
+                           kind=kind)
+    np.testing.assert_array_equal(host(out), g[f"st{k}_{'ip' if kind == 'ip' else 'pl'}_expect"])
+
+
+@pytest.mark.parametrize("mode", list(RAGGED_MODES))
+def test_ref_vectors_fused_ragged(gpu, monkeypatch, mode):
+    ragged_mode(monkeypatch, mode)
+    g = ref_vectors()
+    hdr, pay = wc.cksum_ip_udp_ragged(dev_u8(g["pl_blob"], gpu), to_dev(g["fu_off"], gpu),
+                                      to_dev(g["fu_len"], gpu))
+    np.testing.assert_array_equal(host(hdr), g["fu_hdr_expect"])
+    np.testing.assert_array_equal(host(pay), g["fu_pl_expect"])
+
+
+@pytest.mark.parametrize("k", range(len(refcases.ST_SHAPES)))
+def test_ref_vectors_fused_strided(gpu, k):
+    g = ref_vectors()
+    length, stride = refcases.ST_SHAPES[k]
+    hdr, pay = wc.cksum_ip_udp_strided(dev_u8(g[f"st{k}_blob"], gpu, pad=0), stride, length,
+                                       refcases.ST_N)
+    np.testing.assert_array_equal(host(hdr), g[f"st{k}_hdr_expect"])
+    np.testing.assert_array_equal(host(pay), g[f"st{k}_pl_expect"])
+
+
+@pytest.mark.parametrize("register", [False, True])
+@pytest.mark.parametrize("group,kind", [("ip", "ip"), ("pl", "payload")])
+def test_ref_vectors_host(gpu, group, kind, register):
+    """wc_cksum_host on pageable and registered memory: the whole group (one
+    zero-copy launch or the pipeline), then its first 256 packets of at most
+    4064 bytes, which a registered buffer hands to the resident server."""
+    g = ref_vectors()
+    buf = g[group + "_blob"].copy()
+    offs, lens, want = g[group + "_off"], g[group + "_len"], g[group + "_expect"]
+    few = np.flatnonzero(lens <= 4064)[:256]
+    if register:
+        wc.host_register(buf)
+    try:
+        got = wc.cksum_host(buf, offs, lens, kind=kind)
+        s0 = wc.server_stats()
+        small = wc.cksum_host(buf, offs[few], lens[few], kind=kind)
+        s1 = wc.server_stats()
+    finally:
+        if register:
+            wc.host_unregister(buf)
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(small, want[few])
+    assert (s1["served"] - s0["served"], s1["fallbacks"] - s0["fallbacks"]) == (int(register), 0)
+
+
+@pytest.mark.parametrize("register", [False, True])
+def test_ref_vectors_fused_host(gpu, register):
+    g = ref_vectors()
+    buf = g["pl_blob"].copy()
+    if register:
+        wc.host_register(buf)
+    try:
+        hdr, pay = wc.cksum_ip_udp_host(buf, g["fu_off"], g["fu_len"])
+        s0 = wc.server_stats()
+        hdr_s, pay_s = wc.cksum_ip_udp_host(buf, g["fu_off"][:256], g["fu_len"][:256])
+        s1 = wc.server_stats()
+    finally:
+        if register:
+            wc.host_unregister(buf)
+    np.testing.assert_array_equal(hdr, g["fu_hdr_expect"])
+    np.testing.assert_array_equal(pay, g["fu_pl_expect"])
+    np.testing.assert_array_equal(hdr_s, g["fu_hdr_expect"][:256])
+    np.testing.assert_array_equal(pay_s, g["fu_pl_expect"][:256])
+    assert (s1["served"] - s0["served"], s1["fallbacks"] - s0["fallbacks"]) == (int(register), 0)
+
+
+def test_ref_vectors_scalar_dropin(gpu):
+    """ip_cksum / payload_cksum under the reference's own names, 64 cases of
+    each spread over the groups (the 65535-byte wrap packet among them)."""
+    g = ref_vectors()
+    blob, offs, lens = g["ip_blob"], g["ip_off"], g["ip_len"]
+    for i in np.linspace(0, offs.size - 1, 64).astype(int).tolist():
+        o, n = int(offs[i]), int(lens[i])
+        assert wc.ip_cksum(blob[o:o + max(n, 1)], n) == g["ip_expect"][i], i
+    blob, offs, lens = g["pl_blob"], g["pl_off"], g["pl_len"]
+    pick = set(np.linspace(0, offs.size - 1, 63).astype(int).tolist())
+    pick.add(int(np.argmax(lens)))
+    assert len(pick) == 64
+    for i in sorted(pick):
+        o, n = int(offs[i]), int(lens[i])
+        assert wc.payload_cksum(blob[o:o + max(n, 40)], n) == g["pl_expect"][i], i
+
+
+def test_ref_vectors_tx_seal(gpu):
+    """wc_tx_seal_ragged on Ethernet frames around the fu packets: the status
+    codes and both values are the recorded ones (tests/tx_model.py's chain,
+    the two checksums by the reference with both fields zeroed), and the two
+    fields of every sealed frame hold them, stored raw."""
+    g = ref_vectors()
+    buf, offs, lens = g["tx_buf"], g["tx_off"], g["tx_len"]
+    d = to_dev(buf, gpu)
+    status, hdr, udp, _ = wc.tx_seal_ragged(d, to_dev(offs, gpu), to_dev(lens, gpu))
+    np.testing.assert_array_equal(status.cpu().numpy(), g["tx_status"])
+    np.testing.assert_array_equal(hdr.cpu().numpy().view(np.uint16), g["tx_hdr_expect"])
+    np.testing.assert_array_equal(udp.cpu().numpy().view(np.uint16), g["tx_udp_expect"])
+    sealed = d.cpu().numpy()
+
+    def field(at):  # a native uint16 at any address
+        return int(sealed[at]) | (int(sealed[at + 1]) << 8)
+
+    checked = 0
+    for i, o in enumerate(offs.astype(np.int64).tolist()):
+        ip = o + 14
+        v4 = sealed[ip] >> 4 == 4
+        hl = int(sealed[ip] & 0x0F) * 4 if v4 else 40
+        if g["tx_status"][i] in (tx_model.SEALED, tx_model.IP_ONLY):
+            assert v4 or g["tx_status"][i] == tx_model.SEALED
+            if v4:
+                assert field(ip + 10) == g["tx_hdr_expect"][i], i
+        if g["tx_status"][i] == tx_model.SEALED:
+            assert field(ip + hl + 6) == g["tx_udp_expect"][i], i
+            checked += 1
+    assert checked > 300
+
+
+def test_live_reference_ragged(gpu):
+    """One live pass where the reference's object came with the tree: 2000
+    fresh wild packets, the kernels against the object itself.  (The recorded
+    results above are the tests that count; this one may skip.)"""
+    from oracle import ref_oracle
+    if not ref_oracle.available():
+        pytest.skip("no oracle/_ref/libwc_ref.so on this host and no reference tree to build it")
+    rng = np.random.default_rng(77)
+    buf, offs, lens = pack(random_packets(rng, 2000, max_payload=1472, wild=True), 1, 3)
+    got = host(wc.cksum_ragged(dev_u8(buf, gpu), to_dev(offs, gpu), to_dev(lens, gpu),
+                               kind="payload"))
+    np.testing.assert_array_equal(got, ref_oracle.cksum_ragged(buf, offs, lens, kind=1))
 
 
 # ---------------------------------------------------------------------------

@@ -12,6 +12,10 @@
 * ``oracle/libwc_oracle.so`` -- TEST INFRASTRUCTURE (parity checker / CPU
   baseline).  Built per host CPU model (``-march=native``), into
   ``oracle/build-<cpu>/`` so a box with a different host CPU rebuilds it.
+* ``oracle/_ref/libwc_ref.so`` -- TEST INFRASTRUCTURE: the reference's own
+  ``in_cksum.c``, compiled unchanged where the reference tree exists
+  (``WC_REFERENCE_DIR``), portable flags, so the copy that travels with the
+  tree loads on a host that has no reference tree.
 
 Staleness is decided by a hash of the sources and flags stored next to each
 library (``<lib>.srchash``), not by file times: a tree copied to another
@@ -36,6 +40,8 @@ INCLUDE = ROOT / "include"
 LIB = PKG / "libwccksum.so"
 LIB_TUNE = PKG / "libwccksum_tune.so"
 ORACLE_DIR = ROOT / "oracle"
+REF_DIR = ORACLE_DIR / "_ref"
+REF_LIB = REF_DIR / "libwc_ref.so"
 
 HIP_SOURCES = [CSRC / "wc_k_strided.hip", CSRC / "wc_k_lean.hip", CSRC / "wc_k_seg.hip",
                CSRC / "wc_k_flat.hip",
@@ -187,13 +193,58 @@ def build_oracle(force: bool = False, verbose: bool = False) -> Path:
     return out
 
 
+def reference_dir() -> Path:
+    """Where the reference tree lies (WC_REFERENCE_DIR); it exists on a
+    development host and not on a GPU host."""
+    return Path(os.environ.get("WC_REFERENCE_DIR") or "/root/reference")
+
+
+def _ref_deps(ref: Path) -> list:
+    """in_cksum.c, every header it can include (the reference's own headers
+    and the template of the generated config.h) and this project's recipe."""
+    headers = sorted((ref / "lib" / "src").glob("*.h")) \
+        + sorted((ref / "lib" / "include" / "warpcore").glob("*.h*"))
+    return [ref / "lib" / "src" / "in_cksum.c", *headers,
+            ORACLE_DIR / "ref_driver.c", ORACLE_DIR / "Makefile"]
+
+
+def build_ref(force: bool = False, verbose: bool = False):
+    """Compile the reference's own in_cksum.c into oracle/_ref/libwc_ref.so
+    (test infrastructure: the object the restatements are pinned to), by the
+    `ref` target of oracle/Makefile.  Without a reference tree -- a GPU host
+    -- nothing is built or removed: whatever oracle/_ref/ holds came with the
+    tree and is kept.  Returns the library's path, or None if there is none."""
+    out = REF_LIB
+    ref = reference_dir()
+    # os.path.isfile: False, not an exception, for a tree this user cannot read
+    if not os.path.isfile(ref / "lib" / "src" / "in_cksum.c"):
+        return out if out.exists() else None
+    deps = _ref_deps(ref)
+    if not force and not _stale(out, deps, ["ref"]):
+        return out
+    with _build_lock(out):
+        if not force and not _stale(out, deps, ["ref"]):
+            return out  # another process built it while this one waited
+        tmp = out.with_name(f"{out.name}.{os.getpid()}.tmp")
+        cmd = ["make", "-s", "-C", str(ORACLE_DIR), f"WC_REFERENCE_DIR={ref}",
+               f"REF_DIR={REF_DIR}", f"REF_OUT={tmp}", "ref"]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, out)
+        _stamp(out).write_text(_src_hash(deps, ["ref"]) + "\n")
+    return out
+
+
 def build_all(force: bool = False, verbose: bool = False, tuning: bool = True) -> None:
     """The product library, the tuning build (the tests pin every path knob's
-    kernels through it) and the oracle."""
+    kernels through it), the oracle and, where the reference tree exists, the
+    reference's own checksum object."""
     build_lib(force=force, verbose=verbose)
     if tuning:
         build_lib(force=force, verbose=verbose, tuning=True)
     build_oracle(force=force, verbose=verbose)
+    build_ref(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":
