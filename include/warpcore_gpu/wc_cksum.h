@@ -130,6 +130,76 @@ int wc_rx_verdict_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
                        const uint16_t *h_frame_len, uint64_t n, uint8_t *h_verdict,
                        uint64_t *h_drops);
 
+/* --- RX delivery: per-frame UDP records and index lists ------------------ */
+
+/* What udp_rx puts into the w_iov of an accepted frame (udp.c:101-142,
+ * 163-165), 16 bytes, little-endian, all offsets from the frame's first byte.
+ * All-zero (af == 0) for every frame whose verdict is not WC_RX_OK /
+ * WC_RX_OK_NO_CKSUM. */
+struct wc_rx_record {
+    uint16_t data_off; /* i->buf: 14 + hl + 8                                  */
+    uint16_t data_len; /* i->len: (uint16_t)(MIN(udp->len, ip_plen) - 8), as the
+                          reference computes it, wrap included; for OK_NO_CKSUM
+                          the reference never holds it against the slot length,
+                          and neither does the record                          */
+    uint16_t sport;    /* udp->sport as stored (network-order bytes), udp.c:141 */
+    uint16_t dport;    /* udp->dport as stored, udp.c:142                       */
+    uint8_t af;        /* 4 or 6                                               */
+    uint8_t tos;       /* i->flags: ip4->tos, or ip6_tos(vtcecnfl) (ip6.h:77-81)*/
+    uint8_t ttl;       /* ip4->ttl / ip6->hlim                                 */
+    uint8_t hl;        /* ip_hdr_len: ip4_hl(vhl) or 40                        */
+    uint16_t src_off;  /* ip->src: 14 + 12 (IPv4), 14 + 8 (IPv6)               */
+    uint16_t dst_off;  /* ip->dst: 14 + 16 (IPv4), 14 + 24 (IPv6)              */
+};
+
+/* Sets of verdict classes, for wc_rx_select. */
+#define WC_RX_MASK(v) (1u << (v))
+#define WC_RX_MASK_DELIVER (WC_RX_MASK(WC_RX_OK) | WC_RX_MASK(WC_RX_OK_NO_CKSUM))
+#define WC_RX_MASK_HOST    (WC_RX_MASK(WC_RX_NOT_UDP) | WC_RX_MASK(WC_RX_NOT_IP))
+
+/* Bytes of d_scratch the two calls below need for n frames (pure arithmetic,
+ * no GPU; 0 for n = 0, never decreasing in n).  The scratch is the caller's
+ * (device memory, 4-byte aligned, one per call in flight): the device calls
+ * take no library lock and may run concurrently on several streams. */
+uint64_t wc_rx_select_scratch(uint64_t n);
+
+/* d_list[0 .. *d_count) = the indices i, ascending, of the frames with
+ * (mask >> d_verdict[i]) & 1 (codes >= 32 never match); *d_count (a device
+ * uint64) is written, not accumulated; entries past *d_count are left as they
+ * were, so d_list needs as many entries as can match (n always suffices).
+ * n = 0 is WC_OK, writes *d_count = 0 where d_count is given, and looks at
+ * no other pointer (all may be NULL); n > 2^32 is WC_EINVAL.  Asynchronous on `stream`:
+ * three short launches, no atomic and no wait between workgroups. */
+int wc_rx_select(const uint8_t *d_verdict, uint64_t n, uint32_t mask,
+                 uint32_t *d_list, uint64_t *d_count, void *d_scratch, void *stream);
+
+/* wc_rx_verdict_ragged -- the same verdicts and *d_drops for the same frames
+ * -- plus d_rec[i] for every frame (d_rec 16-byte aligned, as any device
+ * allocation is), and, with d_list non-NULL,
+ * wc_rx_select(d_verdict, n, WC_RX_MASK_DELIVER, ...) behind it on the same
+ * stream.  d_list and d_count go together (both or neither): that is checked
+ * first, for every n, so a count without a list is WC_EINVAL for n = 0 too
+ * (unlike wc_rx_select, which for n = 0 takes a lone count).  Then n = 0 is
+ * WC_OK, writes *d_count = 0 if the pair is given, and looks at no other
+ * pointer.  d_scratch may be NULL only when d_list is.  No header is parsed on the host, and no byte
+ * outside a frame is read: every field of a record lies in bytes the checks
+ * before WC_RX_OK / WC_RX_OK_NO_CKSUM have placed inside the frame. */
+int wc_rx_deliver_ragged(const void *d_base, const uint64_t *d_off,
+                         const uint16_t *d_frame_len, uint64_t n, uint8_t *d_verdict,
+                         struct wc_rx_record *d_rec, uint32_t *d_list, uint64_t *d_count,
+                         uint64_t *d_drops, void *d_scratch, void *stream);
+
+/* Host-memory frames, by the paths of wc_rx_verdict_host except the resident
+ * server (a zero-copy launch, in-place streaming or the pipeline);
+ * synchronous.  h_list / *h_count (optional, both or neither -- checked
+ * first, as above, for n = 0 too) = the WC_RX_MASK_DELIVER list, built by the
+ * calling thread from the verdict bytes; *h_drops (optional) = the drop count.
+ * n = 0 is WC_OK and writes 0 to whichever counts are given. */
+int wc_rx_deliver_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
+                       const uint16_t *h_frame_len, uint64_t n, uint8_t *h_verdict,
+                       struct wc_rx_record *h_rec, uint32_t *h_list, uint64_t *h_count,
+                       uint64_t *h_drops);
+
 /* --- TX seal: both checksums computed and stored in the frames ----------- */
 
 /* What mk_ip4_hdr and udp_tx do to a frame (ip4.c:184-186, udp.c:209-213),

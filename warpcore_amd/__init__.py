@@ -16,6 +16,8 @@ from .cksum import (KIND_IP, KIND_PAYLOAD, SclkProbe, WcError, cksum_host, cksum
                     rx_verdict_ragged, rx_verdict_host, RX_NAMES, RX_DROPS,
                     RX_OK, RX_OK_NO_CKSUM, RX_BAD_IP_CKSUM, RX_BAD_UDP_CKSUM, RX_SHORT,
                     RX_FRAGMENT, RX_BAD_VERSION, RX_NOT_UDP, RX_NOT_IP, RX_TRUNCATED,
+                    rx_deliver_ragged, rx_deliver_host, rx_select, rx_select_scratch,
+                    RX_RECORD, RX_MASK_DELIVER, RX_MASK_HOST,
                     tx_seal_ragged, tx_seal_host, TX_NAMES, TX_ERRORS,
                     TX_SEALED, TX_SEALED_ZERO_UDP, TX_IP_ONLY, TX_NOT_UDP, TX_NOT_IP,
                     TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED)
@@ -31,6 +33,8 @@ __all__ = [
     "verify_strided", "version", "shard_devices", "rx_verdict_ragged", "rx_verdict_host",
     "RX_NAMES", "RX_DROPS", "RX_OK", "RX_OK_NO_CKSUM", "RX_BAD_IP_CKSUM", "RX_BAD_UDP_CKSUM",
     "RX_SHORT", "RX_FRAGMENT", "RX_BAD_VERSION", "RX_NOT_UDP", "RX_NOT_IP", "RX_TRUNCATED",
+    "rx_deliver_ragged", "rx_deliver_host", "rx_select", "rx_select_scratch", "RX_RECORD",
+    "RX_MASK_DELIVER", "RX_MASK_HOST",
     "tx_seal_ragged", "tx_seal_host", "TX_NAMES", "TX_ERRORS", "TX_SEALED",
     "TX_SEALED_ZERO_UDP", "TX_IP_ONLY", "TX_NOT_UDP", "TX_NOT_IP", "TX_BAD_VERSION",
     "TX_MALFORMED", "TX_TRUNCATED",

@@ -45,7 +45,8 @@ REF_LIB = REF_DIR / "libwc_ref.so"
 
 HIP_SOURCES = [CSRC / "wc_k_strided.hip", CSRC / "wc_k_lean.hip", CSRC / "wc_k_seg.hip",
                CSRC / "wc_k_flat.hip",
-               CSRC / "wc_k_rx.hip", CSRC / "wc_k_tx.hip", CSRC / "wc_k_serve.hip",
+               CSRC / "wc_k_rx.hip", CSRC / "wc_k_rxsel.hip", CSRC / "wc_k_tx.hip",
+               CSRC / "wc_k_serve.hip",
                CSRC / "wc_rccl.cpp",
                CSRC / "wc_k_synth.hip",
                CSRC / "wc_rt_config.cpp", CSRC / "wc_rt_plan.cpp", CSRC / "wc_rt_rx.cpp",

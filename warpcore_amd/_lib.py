@@ -35,6 +35,10 @@ SIGNATURES = {
     "wc_cksum_ip_udp_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "wc_rx_verdict_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "wc_rx_verdict_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "wc_rx_select_scratch": (_u64, [_u64]),
+    "wc_rx_select": (_int, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "wc_rx_deliver_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_rx_deliver_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "wc_cksum_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _int]),

@@ -370,6 +370,122 @@ def rx_verdict_host(buf: np.ndarray, offsets: np.ndarray,
 
 
 # --------------------------------------------------------------------------
+# RX delivery (what udp_rx puts into the w_iov, and which frames to walk).
+
+# struct wc_rx_record (include/warpcore_gpu/wc_cksum.h): 16 bytes, little-endian
+RX_RECORD = np.dtype([("data_off", "<u2"), ("data_len", "<u2"), ("sport", "<u2"),
+                      ("dport", "<u2"), ("af", "u1"), ("tos", "u1"), ("ttl", "u1"),
+                      ("hl", "u1"), ("src_off", "<u2"), ("dst_off", "<u2")])
+assert RX_RECORD.itemsize == 16
+RX_MASK_DELIVER = (1 << RX_OK) | (1 << RX_OK_NO_CKSUM)
+RX_MASK_HOST = (1 << RX_NOT_UDP) | (1 << RX_NOT_IP)
+_RX_SELECT_MAX = 1 << 32
+
+
+def rx_select_scratch(n: int) -> int:
+    """Bytes of device scratch wc_rx_select needs for n frames (no GPU)."""
+    return int(_lib.active().wc_rx_select_scratch(int(n)))
+
+
+def _select_scratch(n: int, device) -> torch.Tensor:
+    # int32 elements: a torch allocation is aligned far beyond the 4 bytes asked
+    return torch.empty(max(1, (rx_select_scratch(n) + 3) // 4), dtype=torch.int32, device=device)
+
+
+def rx_select(verdicts: torch.Tensor, mask: int, out: Optional[torch.Tensor] = None,
+              stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ascending indices i with ``(mask >> verdicts[i]) & 1`` (wc_rx_select;
+    ``RX_MASK_DELIVER``, ``RX_MASK_HOST`` or any set of ``1 << RX_*``): a
+    uint32 device list of ``verdicts.numel()`` entries whose first ``count``
+    are written -- the rest keep what they held -- and ``count`` as a 1-element
+    int64 device tensor.  Asynchronous; the scratch is allocated here."""
+    _same_device(verdicts)
+    if verdicts.element_size() != 1 or not verdicts.is_contiguous():
+        raise ValueError("verdicts must be a contiguous 1-byte device tensor")
+    n = verdicts.numel()
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    if not 0 <= int(mask) <= 0xFFFFFFFF:
+        raise ValueError("mask is a uint32 of 1 << RX_* bits")
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint32, device=verdicts.device)
+    if out.numel() < n or out.element_size() != 4 or not out.is_contiguous() \
+            or out.device != verdicts.device:
+        raise ValueError(f"out must be a contiguous 4-byte tensor of >= n entries on "
+                         f"{verdicts.device}")
+    count = torch.zeros(1, dtype=torch.int64, device=verdicts.device)
+    scratch = _select_scratch(n, verdicts.device)
+    with _on_device(verdicts.device):
+        _check("wc_rx_select", _lib.active().wc_rx_select(
+            verdicts.data_ptr(), n, int(mask), out.data_ptr(), count.data_ptr(),
+            scratch.data_ptr(), _stream_ptr(stream, verdicts.device)))
+    return out, count
+
+
+def rx_deliver_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                      want_list: bool = True, stream=None, check: bool = True,
+                      out_list: Optional[torch.Tensor] = None):
+    """rx_verdict_ragged plus delivery (wc_rx_deliver_ragged): returns
+    ``(verdicts uint8, records, list, count, drops)`` -- ``records`` an
+    ``(n, 16)`` uint8 device tensor, one struct wc_rx_record per frame (on the
+    host: ``records.cpu().numpy().view(RX_RECORD)``), all-zero unless the
+    verdict is RX_OK / RX_OK_NO_CKSUM; ``list`` / ``count`` as rx_select gives
+    them for ``RX_MASK_DELIVER`` (None, None with ``want_list=False``);
+    ``drops`` as rx_verdict_ragged.  No header is parsed on the host."""
+    _same_device(base, offsets=offsets, lengths=frame_lens)
+    n = _check_ragged_shapes(offsets, frame_lens)
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    if not base.is_contiguous():
+        raise ValueError("base must be contiguous")
+    if check and n:
+        _ragged_bounds(_nbytes(base), offsets, frame_lens, KIND_IP)
+    d = base.device
+    verdicts = torch.empty(n, dtype=torch.uint8, device=d)
+    records = torch.empty((n, RX_RECORD.itemsize), dtype=torch.uint8, device=d)
+    drops = torch.zeros(1, dtype=torch.int64, device=d)
+    lst = cnt = scratch = None
+    if want_list:
+        # The pointer handed to the library comes from a tensor that is never
+        # empty (an empty one, a zero-length slice included, has a NULL data
+        # pointer, which would read as "no list"); only what is returned is
+        # cut to n entries.
+        own = out_list is None
+        lst = torch.empty(max(n, 1), dtype=torch.uint32, device=d) if own else out_list
+        if lst.numel() < max(n, 1) or lst.element_size() != 4 or not lst.is_contiguous() \
+                or lst.device != d:
+            raise ValueError(f"out_list must be a contiguous 4-byte tensor of >= max(n, 1) "
+                             f"entries on {d}")
+        cnt = torch.zeros(1, dtype=torch.int64, device=d)
+        scratch = _select_scratch(n, d)
+    with _on_device(d):
+        _check("wc_rx_deliver_ragged", _lib.active().wc_rx_deliver_ragged(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, verdicts.data_ptr(),
+            records.data_ptr(), lst.data_ptr() if want_list else None,
+            cnt.data_ptr() if want_list else None, drops.data_ptr(),
+            scratch.data_ptr() if want_list else None, _stream_ptr(stream, d)))
+    if want_list and own:
+        lst = lst[:n]
+    return verdicts, records, lst, cnt, drops
+
+
+def rx_deliver_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray):
+    """rx_deliver_ragged over host memory (wc_rx_deliver_host, synchronous):
+    ``(uint8 verdicts, RX_RECORD records, uint32 delivered-frame indices,
+    drop count)``."""
+    buf, off, lens = _host_batch_args(buf, offsets, frame_lens)
+    n = off.size
+    verdicts = np.empty(n, dtype=np.uint8)
+    records = np.zeros(n, dtype=RX_RECORD)
+    lst = np.empty(max(n, 1), dtype=np.uint32)  # (never empty: its pointer must not be NULL)
+    count, drops = ctypes.c_uint64(), ctypes.c_uint64()
+    _check("wc_rx_deliver_host", _lib.active().wc_rx_deliver_host(
+        buf.ctypes.data, buf.size, off.ctypes.data, lens.ctypes.data, n, verdicts.ctypes.data,
+        records.ctypes.data, lst.ctypes.data, ctypes.byref(count), ctypes.byref(drops)))
+    return verdicts, records, lst[:int(count.value)].copy(), int(drops.value)
+
+
+# --------------------------------------------------------------------------
 # TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
 
 # enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)

@@ -177,7 +177,20 @@ constexpr uint32_t kRxTallyWords = 1024;
 hipError_t launch_rx_verdict(const void *base, const uint64_t *offs, const uint16_t *flens,
                              uint64_t n, uint8_t *verdict, uint64_t *drops, bool nt,
                              hipStream_t st, int mode = 0, uint32_t *tally = nullptr,
-                             uint32_t gen = 0, int max_grid = 0);
+                             uint32_t gen = 0, int max_grid = 0, void *rec = nullptr);
+// `rec` (16-byte aligned, n struct wc_rx_record; the deliver calls): the
+// DELIVER kernels also write every frame's delivery record.  They exist with
+// transposed header loads and without SKIP only: kRxHdrT is implied and
+// kRxSkip ignored.
+
+// Stable compaction of verdict bytes (wc_k_rxsel.hip): list[0 .. *count) = the
+// indices i < n, ascending, with (mask >> verdict[i]) & 1 (codes >= 32 never
+// match); *count is stored.  Three launches on `st`: per-block match counts
+// into `scratch` (rxsel_scratch_bytes(n) bytes, 4-byte aligned), one
+// workgroup's exclusive scan of them, the scatter.  n <= 2^32.
+uint64_t rxsel_scratch_bytes(uint64_t n);
+hipError_t launch_rx_select(const uint8_t *verdict, uint64_t n, uint32_t mask, uint32_t *list,
+                            uint64_t *count, void *scratch, hipStream_t st);
 
 // TX seal of Ethernet frames [base + offs[i], + flens[i]) (wc_k_tx.hip): both
 // checksums computed with their fields taken as 0 and stored raw into the

@@ -207,6 +207,65 @@ __device__ __forceinline__ RxParse rx_parse_slow(uint64_t fa, uint32_t flen, boo
     return rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
 }
 
+// struct wc_rx_record (wc_cksum.h) of a frame the parse accepts -- kRxOk here
+// is "OK unless the UDP sum then fails" --, 16 zero bytes for any other: what
+// udp_rx puts into the w_iov (udp.c:101-142, 163-165), as four little-endian
+// words.  Every field lies in bytes hdr_in and udp_in have placed inside the
+// frame.
+__device__ __forceinline__ u32x4 rx_record(const FrameHdr &f, uint32_t verdict)
+{
+    const uint32_t hl = f.x.hl;
+    const uint32_t g0 = f.g0;
+    const uint32_t ulen = ((g0 & 0xFFu) << 8) | ((g0 >> 8) & 0xFFu);
+    const uint32_t dlen = (min(ulen, f.x.ip_plen) - 8u) & 0xFFFFu; // udp.c:128-129, its wrap
+    const bool v4 = f.x.v4;
+    u32x4 r;
+    r.x = (14u + hl + 8u) | (dlen << 16);                    // data_off, data_len
+    r.y = f.pw;                                              // sport, dport as stored
+    r.z = (v4 ? 4u : 6u) | (f.tt << 8) | (hl << 24);         // af, tos, ttl, hl
+    r.w = v4 ? (26u | (30u << 16)) : (22u | (38u << 16));    // src_off, dst_off
+    // (masked, not selected against a zero vector: store data needs registers,
+    // and the compiler kept a hoisted {0, 0, 0, 0} live across the whole tile
+    // loop -- in scratch, at the 128-VGPR cap)
+    const uint32_t take = verdict == kRxOk || verdict == kRxOkNoCksum ? ~0u : 0u;
+    return u32x4{r.x & take, r.y & take, r.z & take, r.w & take};
+}
+
+// Sixteen zero bytes of store data made where they are stored (see rx_record).
+__device__ __forceinline__ u32x4 rx_zero_record()
+{
+    uint32_t z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    return u32x4{z, z, z, z};
+}
+
+// One record out, as a streaming (nontemporal) store.
+__device__ __forceinline__ void rx_rec_store(u32x4 *rec, uint64_t p, const u32x4 &r)
+{
+    __builtin_nontemporal_store(r, &rec[p]);
+}
+
+// rx_parse / rx_parse_slow for the DELIVER kernels: the same decision on a
+// parse that also returns the record's fields.
+__device__ __forceinline__ RxParse rx_parse_rec(const u32x4 (&c)[5], uint64_t fa, uint32_t flen,
+                                                bool valid, bool &slow, u32x4 &rec)
+{
+    const FrameHdr f = frame_hdr<true>(c, fa, flen);
+    slow = valid && f.x.hdr_in && f.x.v4 && (f.x.hl > 40u || f.x.hl < 20u);
+    const RxParse h = rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
+    rec = rx_record(f, slow ? kRxTruncated : h.verdict); // (a slow lane's comes from the slow parse)
+    return h;
+}
+
+__device__ __forceinline__ RxParse rx_parse_slow_rec(uint64_t fa, uint32_t flen, bool valid,
+                                                     uint64_t zero, u32x4 &rec)
+{
+    const FrameHdr f = frame_hdr_slow<true>(fa, flen, valid, zero);
+    const RxParse h = rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
+    rec = rx_record(f, h.verdict);
+    return h;
+}
+
 // Kernel modes (launch_rx_verdict), all giving the same verdicts:
 //   EARLY  the header parse completes BEFORE the stream, which then carries
 //          only the frames that need the UDP check and only their checked
@@ -234,12 +293,30 @@ __device__ __forceinline__ RxParse rx_parse_slow(uint64_t fa, uint32_t flen, boo
 // ARP frames 91.8 -> 89.1 us, the others unchanged: profiles/ab_r06m_rx_waves.log).
 constexpr int kRxSpan = 15; // XCD super-blocks of 2^15 tiles, as the seg kernel's
 
-template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY>
+//   DELIVER (wc_rx_deliver_*; HT, no SKIP) also writes rec[p], the frame's
+//          struct wc_rx_record, one 16-byte store per lane where the parse
+//          has it (inside the Late hook, or right after rx_parse), so that no
+//          record register lives across the stream: a real record where the
+//          parse accepts the frame pending the UDP sum, zeros otherwise; the
+//          few lanes whose UDP sum then fails store zeros over theirs (the
+//          same lane, the same address: in program order).
+// The record array is a trailing parameter PACK: empty for the plain verdict
+// kernels, whose signature, name and code stay what they were before DELIVER
+// (tools/kres.sh), one `u32x4 *` for the DELIVER kernels.
+__device__ __forceinline__ u32x4 *rx_rec_arg() { return nullptr; }
+__device__ __forceinline__ u32x4 *rx_rec_arg(u32x4 *rec) { return rec; }
+
+template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY, typename... Rec>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
 k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
              const uint16_t *__restrict__ flens, uint64_t n, uint8_t *__restrict__ verdict,
-             unsigned long long *__restrict__ drops, uint32_t *__restrict__ tally, uint32_t gen)
+             unsigned long long *__restrict__ drops, uint32_t *__restrict__ tally, uint32_t gen,
+             Rec... rec_arg)
 {
+    constexpr bool DELIVER = sizeof...(Rec) == 1;
+    static_assert(sizeof...(Rec) <= 1, "no record array, or one");
+    static_assert(!DELIVER || (HT && !SKIP), "deliver launches: transposed headers, no SKIP");
+    [[maybe_unused]] u32x4 *const __restrict__ rec = rx_rec_arg(rec_arg...);
     __shared__ FrameLds L;
 
     const int lane = threadIdx.x & 63;
@@ -283,14 +360,37 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
         bool slow = false;
         RxParse h{};
         uint32_t v;
+// rx_parse; DELIVER: and the record it has, stored at once.  (A macro and
+// `if constexpr` around the plain kernels' own statements, not a lambda: the
+// plain kernels must compile to exactly what they were.)
+#define WC_RX_PARSE()                                                          \
+    do {                                                                       \
+        if constexpr (DELIVER) {                                               \
+            u32x4 r_;                                                          \
+            h = rx_parse_rec(c, fa, flen, valid, slow, r_);                    \
+            if (valid)                                                         \
+                rx_rec_store(rec, p, r_);                                      \
+        } else {                                                               \
+            h = rx_parse(c, fa, flen, valid, slow);                            \
+        }                                                                      \
+    } while (0)
+// The UDP sum failed: no record after all.
+#define WC_RX_TAKE_BACK(failed)                                                \
+    do {                                                                       \
+        if constexpr (DELIVER) {                                               \
+            if (failed)                                                        \
+                rx_rec_store(rec, p, rx_zero_record());                        \
+        }                                                                      \
+    } while (0)
         if constexpr (EARLY) {
             headers();
-            h = rx_parse(c, fa, flen, valid, slow);
+            WC_RX_PARSE();
             v = h.verdict;
             const bool need = h.need && !slow;
             const uint32_t r = frame_payload_cksum<NT>(L, lane, ip, h.plen, need, zero);
             if (need)
                 v = r != 0 ? kRxBadUdpCksum : kRxOk; // udp.c:134-139
+            WC_RX_TAKE_BACK(need && r != 0);
         } else {
             constexpr int UNS = kFrameUns;
             using Src = GathSrc<UNS, NT, SKIP>;
@@ -308,7 +408,7 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
                 bool need = false;
                 auto late = [&](uint32_t &len, bool &on) {
                     headers();
-                    h = rx_parse(c, fa, flen, valid, slow);
+                    WC_RX_PARSE();
                     need = h.need && !slow;
                     on = need;
                     len = need ? h.plen : 0u;
@@ -331,10 +431,11 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
                 v = h.verdict;
                 if (need)
                     v = r != 0 ? kRxBadUdpCksum : kRxOk; // udp.c:134-139
+                WC_RX_TAKE_BACK(need && r != 0);
                 wave_order(); // the tables are rewritten by the next tile
             } else {
                 headers();
-                h = rx_parse(c, fa, flen, valid, slow);
+                WC_RX_PARSE();
                 v = h.verdict;
             }
         }
@@ -348,11 +449,23 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
             }
         }
         if (__ballot(slow)) { // IPv4 headers with more than 20 B of options, IHL < 5
-            const RxParse hs = rx_parse_slow(fa, flen, slow, zero);
-            if (slow) {
-                v = hs.verdict;
-                if (hs.need)
-                    v = lane_payload_exact<NT>(hs.ip, hs.plen) != 0 ? kRxBadUdpCksum : kRxOk;
+            if constexpr (DELIVER) { // (stored before the exact sum, taken back after it)
+                u32x4 r;
+                const RxParse hs = rx_parse_slow_rec(fa, flen, slow, zero, r);
+                if (slow) {
+                    rx_rec_store(rec, p, r);
+                    v = hs.verdict;
+                    if (hs.need)
+                        v = lane_payload_exact<NT>(hs.ip, hs.plen) != 0 ? kRxBadUdpCksum : kRxOk;
+                    WC_RX_TAKE_BACK(hs.need && v == kRxBadUdpCksum);
+                }
+            } else {
+                const RxParse hs = rx_parse_slow(fa, flen, slow, zero);
+                if (slow) {
+                    v = hs.verdict;
+                    if (hs.need)
+                        v = lane_payload_exact<NT>(hs.ip, hs.plen) != 0 ? kRxBadUdpCksum : kRxOk;
+                }
             }
         }
         if (valid)
@@ -360,6 +473,8 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
         ndrop += valid && rx_is_drop(v);
         WC_STAMP(4, WC_CLOCK());
     }
+#undef WC_RX_PARSE
+#undef WC_RX_TAKE_BACK
     if (drops) {
         ndrop = group_sum<64>(ndrop);
         if (lane == 0 && ndrop)
@@ -369,21 +484,27 @@ k_rx_verdict(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs
 
 } // namespace
 
-template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY>
+template <bool NT, bool EARLY, bool HT, bool SKIP, bool TALLY, bool DELIVER = false>
 static hipError_t launch_rx_one(const void *base, const uint64_t *offs, const uint16_t *flens,
                                 uint64_t n, uint8_t *verdict, uint64_t *drops, int grid,
-                                hipStream_t st, uint32_t *tally, uint32_t gen)
+                                hipStream_t st, uint32_t *tally, uint32_t gen,
+                                void *rec = nullptr)
 {
-    hipLaunchKernelGGL((k_rx_verdict<NT, EARLY, HT, SKIP, TALLY>), dim3(grid), dim3(64), 0, st,
-                       (const uint8_t *)base, offs, flens, n, verdict,
-                       (unsigned long long *)drops, tally, gen);
+    if constexpr (DELIVER)
+        hipLaunchKernelGGL((k_rx_verdict<NT, EARLY, HT, SKIP, TALLY, u32x4 *>), dim3(grid),
+                           dim3(64), 0, st, (const uint8_t *)base, offs, flens, n, verdict,
+                           (unsigned long long *)drops, tally, gen, (u32x4 *)rec);
+    else
+        hipLaunchKernelGGL((k_rx_verdict<NT, EARLY, HT, SKIP, TALLY>), dim3(grid), dim3(64), 0,
+                           st, (const uint8_t *)base, offs, flens, n, verdict,
+                           (unsigned long long *)drops, tally, gen);
     return hipGetLastError();
 }
 
 hipError_t launch_rx_verdict(const void *base, const uint64_t *offs, const uint16_t *flens,
                              uint64_t n, uint8_t *verdict, uint64_t *drops, bool nt,
                              hipStream_t st, int mode, uint32_t *tally, uint32_t gen,
-                             int max_grid)
+                             int max_grid, void *rec)
 {
     const uint64_t tiles = (n + 63) / 64;
     // One tile per wave (one-shot); max_grid > 0 (WC_RX_GRID, tools) caps the
@@ -396,6 +517,17 @@ hipError_t launch_rx_verdict(const void *base, const uint64_t *offs, const uint1
     const bool early = mode & kRxEarly, ht = mode & kRxHdrT, skip = (mode & kRxSkip) && !early;
     // ADAPT: the host chose EARLY or HT; the kernel tallies
     const bool tal = tally && !skip && ht;
+    if (rec) { // deliver launches: the transposed-header kernels only (HDRT / SKIP ignored)
+#define WC_RXD(N, E, T)                                                        \
+    if (nt == N && early == E && (tally != nullptr) == T)                      \
+        return launch_rx_one<N, E, true, false, T, true>(                      \
+            base, offs, flens, n, verdict, drops, grid, st, T ? tally : nullptr, T ? gen : 0u,  \
+            rec);
+        WC_RXD(true, false, false) WC_RXD(true, false, true) WC_RXD(true, true, false)
+        WC_RXD(true, true, true) WC_RXD(false, false, false) WC_RXD(false, false, true)
+        WC_RXD(false, true, false) WC_RXD(false, true, true)
+#undef WC_RXD
+    }
 #define WC_RX(N, E, H, S, T)                                                   \
     if (nt == N && early == E && ht == H && skip == S && tal == T)             \
         return launch_rx_one<N, E, H, S, T>(base, offs, flens, n, verdict, drops, grid, st,   \

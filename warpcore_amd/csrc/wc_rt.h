@@ -48,6 +48,11 @@ constexpr int kKindFused = 3;
 constexpr int kKindTx = 4;
 constexpr int kKindTxZero = 5;
 constexpr bool kind_is_tx(int kind) { return kind == kKindTx || kind == kKindTxZero; }
+// RX delivery (wc_rx_deliver_host: the DELIVER verdict kernels, lengths =
+// frame lengths): the 1-byte verdicts into the main results, the 16-byte
+// struct wc_rx_record of every frame into the second array.  Never the
+// resident server's (a server result slot is 32 bits).
+constexpr int kKindRxDeliver = 6;
 
 // Small batches over registered memory skip the copy engines: the kernel
 // reads the packets straight out of the page-locked region over PCIe, and
@@ -74,12 +79,18 @@ constexpr OutRow out_row(int kind)
     return kind == kKindRx      ? OutRow{{1, 0, 0}}
            : kind == kKindFused ? OutRow{{2, 2, 0}}
            : kind_is_tx(kind)   ? OutRow{{2, 2, 1}}
+           : kind == kKindRxDeliver ? OutRow{{1, 16, 0}}
                                 : OutRow{{2, 0, 0}};
 }
 static_assert(out_row(WC_CKSUM_IP).is(2, 0, 0) && out_row(WC_CKSUM_PAYLOAD).is(2, 0, 0), "");
 static_assert(out_row(kKindRx).is(1, 0, 0) && out_row(kKindFused).is(2, 2, 0), "");
 static_assert(out_row(kKindTx).is(2, 2, 1) && out_row(kKindTxZero).is(2, 2, 1), "");
-constexpr OutRow kOutCap = out_row(kKindTx); // the widest row: what a buffer set holds
+static_assert(out_row(kKindRxDeliver).is(1, 16, 0), "");
+// The widest row every buffer set holds from its creation.  The deliver
+// kind's 16-byte records are not under it: a set allocates that array of its
+// own at its first deliver batch (BufSet::need), so a process that never
+// delivers pins what it did before.
+constexpr OutRow kOutCap = out_row(kKindTx);
 
 // The caller's result arrays of a host batch, in out_row's order.
 struct HostOuts {
@@ -94,11 +105,21 @@ struct BufView {
     uint64_t *off = nullptr;
     uint16_t *len = nullptr;
     uint8_t *out[kOuts] = {};
+    uint8_t *rec = nullptr; // the deliver kind's second array, once needed
+    // Result array k of a batch of `kind`.
+    uint8_t *out_of(int kind, int k) const
+    {
+        return kind == kKindRxDeliver && k == 1 ? rec : out[k];
+    }
 };
 struct BufSet {
     BufView h, d;
     bool mapped = false;
+    uint64_t pkts = 0;
     int alloc(uint64_t pkts, bool mapped_pinned);
+    // Before a batch of `kind` uses the set: the record array at the first
+    // deliver batch, nothing otherwise.
+    int need(int kind);
     void free(); // (safe on a partly built set)
     // Packets [0, n)'s results of `kind` to the caller's arrays at packet lo.
     void copy_out(int kind, const HostOuts &outs, uint64_t lo, uint64_t n) const;
@@ -360,9 +381,10 @@ int run(const Device &D, const Config &C, const wc::LaunchArgs &args, const Plan
         hipStream_t st);
 
 // --- wc_rt_rx.cpp -------------------------------------------------------------
+// rec: NULL, or the frames' struct wc_rx_record array (the DELIVER kernels).
 hipError_t rx_launch(Device &D, const Config &C, const void *base, const uint64_t *offs,
                      const uint16_t *flens, uint64_t n, uint8_t *verdict, uint64_t *drops,
-                     hipStream_t st);
+                     hipStream_t st, void *rec = nullptr);
 
 // --- wc_rt_server.cpp ---------------------------------------------------------
 constexpr int kSrvFallback = 1; // serve_batch: not served, take the launch path

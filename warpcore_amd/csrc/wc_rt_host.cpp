@@ -1,5 +1,5 @@
 // wc_rt_host.cpp -- host-memory batches (wc_cksum_host, wc_cksum_ip_udp_host,
-// wc_rx_verdict_host, the seal's compute pass, wc_host_register): the
+// wc_rx_verdict_host, wc_rx_deliver_host, the seal's compute pass, wc_host_register): the
 // resident server or one zero-copy launch for a small registered batch, else
 // the in-place stream or the pipelined path (hipMemcpyAsync H2D, kernel, D2H)
 // through pinned staging.  All three launch paths keep their per-batch arrays
@@ -36,6 +36,7 @@ static bool buf_alloc(bool mapped, T *&h, T *&d, uint64_t bytes)
 int BufSet::alloc(uint64_t pkts, bool mapped_pinned)
 {
     mapped = mapped_pinned;
+    this->pkts = pkts;
     bool ok = buf_alloc(mapped, h.off, d.off, pkts * 8);
     ok = ok && buf_alloc(mapped, h.len, d.len, pkts * 2);
     for (int k = 0; k < kOuts && ok; ++k)
@@ -45,6 +46,19 @@ int BufSet::alloc(uint64_t pkts, bool mapped_pinned)
     return ok ? WC_OK : WC_ENOMEM;
 }
 
+int BufSet::need(int kind)
+{
+    if (kind != kKindRxDeliver || h.rec)
+        return WC_OK;
+    if (buf_alloc(mapped, h.rec, d.rec, pkts * out_row(kKindRxDeliver).w[1]))
+        return WC_OK;
+    if (!mapped)
+        (void)hipFree(d.rec);
+    (void)hipHostFree(h.rec);
+    h.rec = d.rec = nullptr;
+    return WC_ENOMEM;
+}
+
 void BufSet::free()
 {
     if (!mapped) { // (a mapped set's device view is the host memory's own)
@@ -52,11 +66,13 @@ void BufSet::free()
         (void)hipFree(d.len);
         for (uint8_t *p : d.out)
             (void)hipFree(p);
+        (void)hipFree(d.rec);
     }
     (void)hipHostFree(h.off);
     (void)hipHostFree(h.len);
     for (uint8_t *p : h.out)
         (void)hipHostFree(p);
+    (void)hipHostFree(h.rec);
     *this = BufSet{};
 }
 
@@ -65,7 +81,7 @@ void BufSet::copy_out(int kind, const HostOuts &outs, uint64_t lo, uint64_t n) c
     const OutRow row = out_row(kind);
     for (int k = 0; k < kOuts; ++k)
         if (row.w[k])
-            memcpy(outs.p[k] + lo * row.w[k], (const void *)h.out[k], n * row.w[k]);
+            memcpy(outs.p[k] + lo * row.w[k], (const void *)h.out_of(kind, k), n * row.w[k]);
 }
 
 int Slot::init(uint64_t pkts, bool mapped_pinned)
@@ -211,6 +227,8 @@ int run_ragged_any(Device &D, const Config &C, const uint8_t *d_base, const BufV
     uint16_t *const d_out = (uint16_t *)b.out[0], *const d_out_hdr = (uint16_t *)b.out[1];
     if (kind == kKindRx)
         return hip_err(rx_launch(D, C, d_base, b.off, b.len, n, b.out[0], nullptr, st));
+    if (kind == kKindRxDeliver)
+        return hip_err(rx_launch(D, C, d_base, b.off, b.len, n, b.out[0], nullptr, st, b.rec));
     if (kind_is_tx(kind)) // compute only: the calling thread makes the stores (wc_rt_tx.cpp)
         return hip_err(wc::launch_tx_seal(
             const_cast<uint8_t *>(d_base), b.off, b.len, n,
@@ -233,6 +251,9 @@ int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
     if (rc)
         return rc;
     ZeroCopy &Z = D.zc;
+    rc = Z.b.need(kind);
+    if (rc)
+        return rc;
     memcpy(Z.b.h.off, h_off, n * 8);
     memcpy(Z.b.h.len, h_len, n * 2);
     rc = run_ragged_any(D, g_cfg, dbase, Z.b.d, n, kind, true, Z.st);
@@ -284,6 +305,8 @@ int host_zc_stream(Device &D, const uint8_t *dbase, const uint64_t *h_off,
         Slot &s = S.slot[b];
         const uint64_t cnt = std::min(per, n - i);
         rc = s.drain(kind, outs); // (chunk k - 2's results: its buffers are free again)
+        if (rc == WC_OK)
+            rc = s.b.need(kind);
         if (rc)
             break;
         memcpy(s.b.h.off, h_off + i, cnt * 8);
@@ -450,6 +473,8 @@ int PipeRun::step()
 {
     PipeSlot &S = P->slot[slot];
     int rc = S.drain(kind, outs);
+    if (rc == WC_OK)
+        rc = S.b.need(kind);
     if (rc)
         return rc;
     const BufView &sh = S.b.h, &sd = S.b.d;
@@ -515,7 +540,8 @@ int PipeRun::step()
     const OutRow row = out_row(kind);
     for (int k = 0; k < kOuts && e == hipSuccess; ++k)
         if (row.w[k])
-            e = hipMemcpyAsync(sh.out[k], sd.out[k], cnt * row.w[k], hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(sh.out_of(kind, k), sd.out_of(kind, k), cnt * row.w[k],
+                               hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipEventRecord(S.done, st);
     if (e != hipSuccess)
@@ -613,7 +639,8 @@ int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
     if (rc)
         return rc;
     const uint8_t *dbase = registered_dptr_locked(h_base, h_bytes);
-    if (dbase && !kind_is_tx(kind) && g_cfg.serve && server_enabled_locked() &&
+    if (dbase && !kind_is_tx(kind) && kind != kKindRxDeliver && g_cfg.serve &&
+        server_enabled_locked() &&
         n <= (uint64_t)g_cfg.serve_max) {
         bool fits = true; // (a fused header adds at most 40 bytes to the span)
         for (uint64_t i = 0; i < n && fits; ++i)

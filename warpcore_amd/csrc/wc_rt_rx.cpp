@@ -1,6 +1,7 @@
-// wc_rt_rx.cpp -- RX verdict launches (wc_rx_verdict_ragged and the host
-// paths' RX batches): the default ADAPT mode picks EARLY or HT per launch
-// from the tallies earlier launches' tiles stored.
+// wc_rt_rx.cpp -- RX verdict launches (wc_rx_verdict_ragged, wc_rx_deliver_ragged
+// and the host paths' RX batches): the default ADAPT mode picks EARLY or HT
+// per launch from the tallies earlier launches' tiles stored; and
+// wc_rx_select, the index lists over the verdict bytes.
 
 #include "wc_rt.h"
 
@@ -23,17 +24,19 @@ std::mutex g_rx_mu;
 // is a partial sample).
 hipError_t rx_launch(Device &D, const Config &C, const void *base, const uint64_t *offs,
                      const uint16_t *flens, uint64_t n, uint8_t *verdict, uint64_t *drops,
-                     hipStream_t st)
+                     hipStream_t st, void *rec)
 {
+    // A deliver launch (rec): the same choice, among the transposed-header
+    // kernels -- WC_RX_HDRT=0 and WC_RX_SKIP=1 are ignored (launch_rx_verdict).
     const int mode = C.rx_mode();
     if (!(mode & wc::kRxAdapt))
         return wc::launch_rx_verdict(base, offs, flens, n, verdict, drops, C.nt != 0, st, mode,
-                                     nullptr, 0u, C.rx_grid);
+                                     nullptr, 0u, C.rx_grid, rec);
     // (wc_gpu_fini frees the tallies under this lock too: test them inside it)
     std::lock_guard<std::mutex> lk(g_rx_mu);
     if (!D.h_rx_tally[0])
         return wc::launch_rx_verdict(base, offs, flens, n, verdict, drops, C.nt != 0, st,
-                                     wc::kRxHdrT, nullptr, 0u, C.rx_grid);
+                                     wc::kRxHdrT, nullptr, 0u, C.rx_grid, rec);
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t from = 0, from_words = 0, from_seen = 0, from_out = 0;
     for (uint32_t back = 1; back < (uint32_t)kRxSets && back <= D.rx_gen; ++back) {
@@ -91,7 +94,7 @@ hipError_t rx_launch(Device &D, const Config &C, const void *base, const uint64_
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0)
                     .count());
     return wc::launch_rx_verdict(base, offs, flens, n, verdict, drops, C.nt != 0, st, m,
-                                 D.d_rx_tally[set], g & 0xFFFFu, C.rx_grid);
+                                 D.d_rx_tally[set], g & 0xFFFFu, C.rx_grid, rec);
 }
 
 } // namespace rt
@@ -115,6 +118,108 @@ int wc_rx_verdict_ragged(const void *d_base, const uint64_t *d_off, const uint16
         return rc;
     return hip_err(rx_launch(*D, C, d_base, d_off, d_frame_len, n, d_verdict, d_drops,
                              (hipStream_t)stream));
+}
+
+uint64_t wc_rx_select_scratch(uint64_t n)
+{
+    return wc::rxsel_scratch_bytes(n);
+}
+
+// Indices are uint32: a batch is at most 2^32 frames.
+static constexpr uint64_t kRxSelectMax = 1ull << 32;
+
+// *d_count = 0 for an empty batch (device memory: on the caller's stream).
+static int rx_count_zero(uint64_t *d_count, void *stream)
+{
+    if (!d_count)
+        return WC_OK;
+    Device *D = nullptr;
+    Config C;
+    int rc = ensure_device(&D, &C);
+    if (rc)
+        return rc;
+    return hip_err(hipMemsetAsync(d_count, 0, sizeof(uint64_t), (hipStream_t)stream));
+}
+
+int wc_rx_select(const uint8_t *d_verdict, uint64_t n, uint32_t mask, uint32_t *d_list,
+                 uint64_t *d_count, void *d_scratch, void *stream)
+{
+    if (n > kRxSelectMax)
+        return WC_EINVAL;
+    if (n == 0)
+        return rx_count_zero(d_count, stream);
+    if (!d_verdict || !d_list || !d_count || !d_scratch || ((uintptr_t)d_scratch & 3u))
+        return WC_EINVAL;
+    Device *D = nullptr;
+    Config C;
+    int rc = ensure_device(&D, &C);
+    if (rc)
+        return rc;
+    return hip_err(wc::launch_rx_select(d_verdict, n, mask, d_list, d_count, d_scratch,
+                                        (hipStream_t)stream));
+}
+
+int wc_rx_deliver_ragged(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
+                         uint64_t n, uint8_t *d_verdict, struct wc_rx_record *d_rec,
+                         uint32_t *d_list, uint64_t *d_count, uint64_t *d_drops, void *d_scratch,
+                         void *stream)
+{
+    static_assert(sizeof(struct wc_rx_record) == 16, "one 16-byte store per frame");
+    if (n > kRxSelectMax || (d_list != nullptr) != (d_count != nullptr))
+        return WC_EINVAL;
+    if (n == 0)
+        return rx_count_zero(d_count, stream);
+    if (!d_base || !d_off || !d_frame_len || !d_verdict || !d_rec || ((uintptr_t)d_rec & 15u))
+        return WC_EINVAL;
+    if (d_list && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
+        return WC_EINVAL;
+    Device *D = nullptr;
+    Config C;
+    int rc = ensure_device(&D, &C);
+    if (rc)
+        return rc;
+    hipError_t e = rx_launch(*D, C, d_base, d_off, d_frame_len, n, d_verdict, d_drops,
+                             (hipStream_t)stream, d_rec);
+    if (e == hipSuccess && d_list)
+        e = wc::launch_rx_select(d_verdict, n, WC_RX_MASK_DELIVER, d_list, d_count, d_scratch,
+                                 (hipStream_t)stream);
+    return hip_err(e);
+}
+
+int wc_rx_deliver_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
+                       const uint16_t *h_frame_len, uint64_t n, uint8_t *h_verdict,
+                       struct wc_rx_record *h_rec, uint32_t *h_list, uint64_t *h_count,
+                       uint64_t *h_drops)
+{
+    if (n > kRxSelectMax || (h_list != nullptr) != (h_count != nullptr))
+        return WC_EINVAL;
+    if (n == 0) {
+        if (h_count)
+            *h_count = 0;
+        if (h_drops)
+            *h_drops = 0;
+        return WC_OK;
+    }
+    if (!h_verdict || !h_rec)
+        return WC_EINVAL;
+    const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n,
+                              {{h_verdict, (uint8_t *)h_rec}}, kKindRxDeliver);
+    if (rc != WC_OK)
+        return rc;
+    // The list and the drop count by the calling thread, once the batch has
+    // drained: one pass over n bytes (the frames are in host memory anyway).
+    uint64_t drops = 0, cnt = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint8_t v = h_verdict[i];
+        drops += WC_RX_IS_DROP(v);
+        if (h_list && (v == WC_RX_OK || v == WC_RX_OK_NO_CKSUM))
+            h_list[cnt++] = (uint32_t)i;
+    }
+    if (h_count)
+        *h_count = cnt;
+    if (h_drops)
+        *h_drops = drops;
+    return WC_OK;
 }
 
 } // extern "C"

@@ -86,15 +86,29 @@ struct FrameHdr {
     uint32_t g0;   // UDP length | checksum << 16 (udp.h:41-46), a native word
     uint32_t ipck; // ip_cksum(ip, hl) of the header as loaded
     uint32_t f_ip; // ip->cksum as loaded, a native word (the TX seal only)
+    // What a delivery record takes beside these (the RX DELIVER kernels only;
+    // 0 from a parse without EXTRA, so every other kernel compiles as before):
+    uint32_t pw; // udp->sport | udp->dport << 16 as stored, the word at 14 + hl
+    uint32_t tt; // tos | ttl << 8 (udp.c:109-110, 119-120; ip6_tos: ip6.h:77-81)
 };
+
+// i->flags and i->ttl from frame bytes 12..15 (f0) and 20..23 (f2).
+__device__ __forceinline__ uint32_t frame_tos_ttl(bool v4, uint32_t f0, uint32_t f2)
+{
+    const uint32_t tos = v4 ? f0 >> 24 : (((f0 >> 16) & 0xFu) << 4) | (f0 >> 28);
+    const uint32_t ttl = v4 ? (f2 >> 16) & 0xFFu : (f2 >> 8) & 0xFFu; // ttl @8 / hlim @7
+    return tos | (ttl << 8);
+}
 
 // The parse in ONE load round, on the five chunks of rx_load (or of the RX
 // kernel's transposed rx_load_t).  Right for IPv6 and for IPv4 headers of
 // 20 <= hl <= 40 bytes; the caller sends every other frame whose header sum
-// it needs through frame_hdr_slow.
+// it needs through frame_hdr_slow.  EXTRA: also the port word and TOS / TTL.
+template <bool EXTRA = false>
 __device__ __forceinline__ FrameHdr frame_hdr(const u32x4 (&c)[5], uint64_t fa, uint32_t flen)
 {
     FrameHdr f;
+    f.pw = f.tt = 0u;
     const uint32_t sf = (uint32_t)(fa & 15u);
     // frame bytes 12..23 start in chunk 0 or 1
     const uint32_t o1 = sf + 12u;
@@ -110,7 +124,21 @@ __device__ __forceinline__ FrameHdr frame_hdr(const u32x4 (&c)[5], uint64_t fa, 
     const u32x4 z4 = {0u, 0u, 0u, 0u};
     const u32x4 xu = ju <= 2u ? c[2] : (ju == 3u ? c[3] : c[4]);
     const u32x4 yu = ju <= 2u ? c[3] : (ju == 3u ? c[4] : z4);
-    f.g0 = win_bytes(xu, yu, yu, u & 15u, 0);
+    if constexpr (EXTRA) {
+        // the UDP header's first 8 bytes, from frame byte 14 + hl: the same
+        // chunks from four bytes earlier (u - 4 >= 34: chunk 2, 3 or 4)
+        const uint32_t up = u - 4u;
+        const uint32_t jp = up >> 4;
+        const u32x4 xp = jp <= 2u ? c[2] : (jp == 3u ? c[3] : c[4]);
+        const u32x4 yp = jp <= 2u ? c[3] : (jp == 3u ? c[4] : z4);
+        uint32_t uw[2];
+        win_rot(xp, yp, yp, up & 15u, uw);
+        f.pw = uw[0];
+        f.g0 = uw[1];
+        f.tt = frame_tos_ttl(f.x.v4, fw[0], fw[2]);
+    } else {
+        f.g0 = win_bytes(xu, yu, yu, u & 15u, 0);
+    }
     // ip_cksum(ip, hl) (ip4.c:110-115) over frame bytes [14, 14 + hl),
     // 20 <= hl <= 40 here (14 + 40 + 15 < 80: inside the five chunks): the
     // header's little-endian words summed header-relative, as csum_oc16 reads
@@ -138,10 +166,12 @@ __device__ __forceinline__ FrameHdr frame_hdr(const u32x4 (&c)[5], uint64_t fa, 
 // The same in two load rounds for this lane's frame [fa, fa + flen), any IHL:
 // the chunks around frame bytes 12..23 first, then, with the IHL known, the
 // UDP fields and the IPv4 header's chunks.  The fallback of frame_hdr.
+template <bool EXTRA = false>
 __device__ __forceinline__ FrameHdr frame_hdr_slow(uint64_t fa, uint32_t flen, bool valid,
                                                    uint64_t zero)
 {
     FrameHdr f;
+    f.pw = f.tt = 0u;
     const uint64_t fend = fa + flen;
     const uint64_t a1 = fa + 12u;
     const Win2 w1 = win2_load(a1, fend, valid && flen > 12u, zero);
@@ -152,7 +182,9 @@ __device__ __forceinline__ FrameHdr frame_hdr_slow(uint64_t fa, uint32_t flen, b
     const uint32_t hl = f.x.hl;
     // The UDP length / checksum fields (udp.h:41-46) at ip + hl + 4, and the
     // IPv4 header's chunks, all issued before any is used.
-    const uint64_t a2 = ip + hl + 4u;
+    // (EXTRA: from the port word at ip + hl on; 8 bytes from any phase lie
+    // inside the window's two chunks)
+    const uint64_t a2 = ip + hl + (EXTRA ? 0u : 4u);
     const Win2 w2 = win2_load(a2, fend, valid && f.x.udp_in, zero);
     const bool hsum = valid && f.x.hdr_in && f.x.v4;
     const uint32_t sip = (uint32_t)(ip & 15u);
@@ -171,7 +203,15 @@ __device__ __forceinline__ FrameHdr frame_hdr_slow(uint64_t fa, uint32_t flen, b
         V += seg_range(hc[k], 16 * k - (int)sip, 0, (int)hl);
     f.ipck = fold_not((ip & 1u) ? __builtin_amdgcn_alignbit(V, V, 24) : V);
     f.f_ip = win_bytes(hc[0], hc[1], hc[2], sip, 2) >> 16; // header bytes 10..11
-    f.g0 = win_bytes(w2.x, w2.y, w2.y, (uint32_t)(a2 & 15u), 0);
+    if constexpr (EXTRA) {
+        uint32_t uw[2];
+        win_rot(w2.x, w2.y, w2.y, (uint32_t)(a2 & 15u), uw);
+        f.pw = uw[0];
+        f.g0 = uw[1];
+        f.tt = frame_tos_ttl(f.x.v4, fw[0], fw[2]);
+    } else {
+        f.g0 = win_bytes(w2.x, w2.y, w2.y, (uint32_t)(a2 & 15u), 0);
+    }
     return f;
 }
 
