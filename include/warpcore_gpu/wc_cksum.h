@@ -200,6 +200,91 @@ int wc_rx_deliver_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
                        struct wc_rx_record *h_rec, uint32_t *h_list, uint64_t *h_count,
                        uint64_t *h_drops);
 
+/* --- RX socket demultiplex: per-frame socket ids, per-socket lists -------- */
+
+/* What udp_rx does next with a delivered frame (udp.c:141-156, 174): it looks
+ * up the socket of local = (af, ip->dst, udp->dport) and remote = (af,
+ * ip->src, udp->sport) -- w_get_sock(w, &local, &remote), then
+ * w_get_sock(w, &local, 0) (backend_netmap.c:481-490), both exact compares
+ * (warpcore.c:644-677) -- and appends the iov to that socket's queue, or
+ * sends an ICMP unreachable when there is none.  The lookup and the grouping
+ * run on the device; the engine's sockets are handed over as a small table. */
+#define WC_RX_DEMUX_MAX_SOCKS 254
+#define WC_RX_SOCK_NONE    0xFE  /* frame not delivered (record af == 0)            */
+#define WC_RX_SOCK_UNBOUND 0xFF  /* delivered, no socket: the host's ICMP unreachable
+                                    decision (udp.c:147-155)                        */
+struct wc_rx_sock {              /* 40 bytes; one bound or connected w_sock         */
+    uint8_t  af;                 /* 4 or 6                                          */
+    uint8_t  connected;          /* 0: bound only (remote ignored); 1: four-tuple   */
+    uint16_t lport, rport;       /* as stored in the UDP header (like record ports) */
+    uint16_t pad;                /* ignored                                         */
+    uint8_t  laddr[16], raddr[16]; /* af 4: bytes 0..3 count, 4..15 ignored         */
+};
+
+/* The socket table: an opaque, position-independent blob of
+ * wc_rx_socktab_bytes(ns) bytes (never decreasing in ns) that
+ * wc_rx_socktab_build writes into h_tab (4-byte aligned) from socks[0 .. ns)
+ * -- an open-addressing hash table holding every socket's whole tuple and its
+ * index, so a probe ends on an exact compare; the same input gives the same
+ * bytes.  Pure host arithmetic: no GPU, no library state.  The caller copies
+ * the blob to the device for wc_rx_demux, again whenever w_bind / w_connect /
+ * w_close change the sockets.  WC_EINVAL: ns > WC_RX_DEMUX_MAX_SOCKS, a NULL
+ * pointer (socks may be NULL for ns = 0), an af other than 4 / 6, connected
+ * other than 0 / 1, or two sockets with the same tuple once the ignored bytes
+ * are dropped (the reference's hash cannot hold such a pair either). */
+uint64_t wc_rx_socktab_bytes(uint32_t ns);
+int      wc_rx_socktab_build(const struct wc_rx_sock *socks, uint32_t ns, void *h_tab);
+
+/* The table's own lookup on the host, by the reference's two steps: the index
+ * of the connected socket with exactly this local and remote pair, else of
+ * the socket bound to the local pair, else WC_RX_SOCK_UNBOUND (also for an af
+ * other than 4 / 6 or a blob that build did not write).  Addresses as
+ * struct wc_rx_sock holds them (af 4: 4 bytes are read), ports as stored. */
+uint8_t  wc_rx_socktab_lookup(const void *h_tab, uint8_t af, const uint8_t *laddr, uint16_t lport,
+                              const uint8_t *raddr, uint16_t rport);
+
+/* Bytes of d_scratch wc_rx_demux needs for n frames with a list (pure
+ * arithmetic, no GPU; 0 for n = 0, never decreasing in n): per-block counts
+ * for the most classes a table can have. */
+uint64_t wc_rx_demux_scratch(uint64_t n);
+
+/* Behind a wc_rx_deliver_ragged of the same frames on the same stream (it
+ * reads d_rec, not the verdicts or frame lengths): d_sock[i] = the index in
+ * the table (d_tab: the blob in device memory, built for ns sockets) of frame
+ * i's socket, WC_RX_SOCK_UNBOUND, or WC_RX_SOCK_NONE where d_rec[i].af == 0.
+ * With d_list / d_start (both or neither: checked first, for every n):
+ * d_list = the delivered frames' indices grouped by socket 0 .. ns - 1, the
+ * unbound frames last, each group in ascending ring order (as sq_insert_tail
+ * queues them); it needs as many entries as frames can be delivered (n always
+ * suffices), entries past the total are left as they were.  d_start has 256
+ * entries whatever ns is: socket s's run is d_list[d_start[s] .. d_start[s+1])
+ * for s < 254 (empty for s >= ns), the unbound run [d_start[254],
+ * d_start[255]), and d_start[255] = the number of delivered frames.  n = 0 is
+ * WC_OK, writes an all-zero d_start if given and looks at no other pointer.
+ * WC_EINVAL: n > 2^32, ns > 254, a NULL d_base / d_off / d_rec / d_tab /
+ * d_sock, d_rec not 16-byte or d_tab not 4-byte aligned, a list without a
+ * 4-byte-aligned d_scratch (the caller's, one per call in flight; it may be
+ * NULL without a list).  The address bytes are read as the aligned 16-byte
+ * chunks that overlap them; they lie inside the frame by the checks that gave
+ * the frame its record.  Asynchronous on `stream`: one launch, three with the
+ * list; no library lock, no atomic, no wait between workgroups, and the same
+ * input gives the same output. */
+int wc_rx_demux(const void *d_base, const uint64_t *d_off, const struct wc_rx_record *d_rec,
+                uint64_t n, const void *d_tab, uint32_t ns, uint8_t *d_sock,
+                uint32_t *d_list, uint64_t *d_start, void *d_scratch, void *stream);
+
+/* wc_rx_deliver_host's verdicts, records and drop count for the same frames,
+ * plus h_sock and (optional, both or neither -- checked first) h_list /
+ * h_start as above, built by the calling thread from the h_sock bytes.
+ * h_tab: the blob in host memory, as wc_rx_socktab_build wrote it for ns
+ * sockets (WC_EINVAL otherwise); the library stages it once per call.
+ * Synchronous; never the resident server.  n = 0 is WC_OK and writes zeros to
+ * h_start and *h_drops where given. */
+int wc_rx_demux_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
+                     const uint16_t *h_frame_len, uint64_t n, const void *h_tab, uint32_t ns,
+                     uint8_t *h_verdict, struct wc_rx_record *h_rec, uint8_t *h_sock,
+                     uint32_t *h_list, uint64_t *h_start, uint64_t *h_drops);
+
 /* --- TX seal: both checksums computed and stored in the frames ----------- */
 
 /* What mk_ip4_hdr and udp_tx do to a frame (ip4.c:184-186, udp.c:209-213),

@@ -18,6 +18,9 @@ from .cksum import (KIND_IP, KIND_PAYLOAD, SclkProbe, WcError, cksum_host, cksum
                     RX_FRAGMENT, RX_BAD_VERSION, RX_NOT_UDP, RX_NOT_IP, RX_TRUNCATED,
                     rx_deliver_ragged, rx_deliver_host, rx_select, rx_select_scratch,
                     RX_RECORD, RX_MASK_DELIVER, RX_MASK_HOST,
+                    rx_socktab_bytes, rx_socktab_build, rx_socktab_lookup, rx_demux,
+                    rx_demux_host, rx_demux_scratch, RX_SOCK, RX_SOCK_NONE, RX_SOCK_UNBOUND,
+                    RX_DEMUX_MAX_SOCKS,
                     tx_seal_ragged, tx_seal_host, TX_NAMES, TX_ERRORS,
                     TX_SEALED, TX_SEALED_ZERO_UDP, TX_IP_ONLY, TX_NOT_UDP, TX_NOT_IP,
                     TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED)
@@ -35,6 +38,8 @@ __all__ = [
     "RX_SHORT", "RX_FRAGMENT", "RX_BAD_VERSION", "RX_NOT_UDP", "RX_NOT_IP", "RX_TRUNCATED",
     "rx_deliver_ragged", "rx_deliver_host", "rx_select", "rx_select_scratch", "RX_RECORD",
     "RX_MASK_DELIVER", "RX_MASK_HOST",
+    "rx_socktab_bytes", "rx_socktab_build", "rx_socktab_lookup", "rx_demux", "rx_demux_host",
+    "rx_demux_scratch", "RX_SOCK", "RX_SOCK_NONE", "RX_SOCK_UNBOUND", "RX_DEMUX_MAX_SOCKS",
     "tx_seal_ragged", "tx_seal_host", "TX_NAMES", "TX_ERRORS", "TX_SEALED",
     "TX_SEALED_ZERO_UDP", "TX_IP_ONLY", "TX_NOT_UDP", "TX_NOT_IP", "TX_BAD_VERSION",
     "TX_MALFORMED", "TX_TRUNCATED",

@@ -39,6 +39,13 @@ SIGNATURES = {
     "wc_rx_select": (_int, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),
     "wc_rx_deliver_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wc_rx_deliver_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "wc_rx_socktab_bytes": (_u64, [_u32]),
+    "wc_rx_socktab_build": (_int, [_vp, _u32, _vp]),
+    "wc_rx_socktab_lookup": (ctypes.c_uint8, [_vp, ctypes.c_uint8, _vp, _u16, _vp, _u16]),
+    "wc_rx_demux_scratch": (_u64, [_u64]),
+    "wc_rx_demux": (_int, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "wc_rx_demux_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp,
+                                _vp]),
     "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "wc_cksum_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _int]),

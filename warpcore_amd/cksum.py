@@ -486,6 +486,139 @@ def rx_deliver_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray
 
 
 # --------------------------------------------------------------------------
+# RX socket demultiplex (udp_rx's w_get_sock calls and per-socket queues).
+
+# struct wc_rx_sock (include/warpcore_gpu/wc_cksum.h): 40 bytes
+RX_SOCK = np.dtype([("af", "u1"), ("connected", "u1"), ("lport", "<u2"), ("rport", "<u2"),
+                    ("pad", "<u2"), ("laddr", "u1", 16), ("raddr", "u1", 16)])
+assert RX_SOCK.itemsize == 40
+RX_DEMUX_MAX_SOCKS = 254
+RX_SOCK_NONE, RX_SOCK_UNBOUND = 0xFE, 0xFF
+_RX_STARTS = 256
+
+
+def rx_socktab_bytes(ns: int) -> int:
+    """Bytes of the socket table of ``ns`` sockets (no GPU)."""
+    return int(_lib.active().wc_rx_socktab_bytes(int(ns)))
+
+
+def rx_socktab_build(socks: np.ndarray) -> np.ndarray:
+    """The socket table of ``socks`` (an ``RX_SOCK`` array, at most 254
+    entries; ports as the UDP header stores them) as wc_rx_socktab_build writes
+    it: a uint8 array to copy to the device for rx_demux or to hand to
+    rx_demux_host.  Pure host arithmetic.  ``ValueError`` for what the library
+    refuses: a bad af / connected field or the same tuple twice."""
+    socks = np.ascontiguousarray(socks, dtype=RX_SOCK).reshape(-1)
+    ns = socks.size
+    if ns > RX_DEMUX_MAX_SOCKS:
+        raise ValueError(f"at most {RX_DEMUX_MAX_SOCKS} sockets (the ids are uint8)")
+    tab = np.zeros(rx_socktab_bytes(ns) // 4, dtype=np.uint32)
+    rc = _lib.active().wc_rx_socktab_build(socks.ctypes.data if ns else None, ns, tab.ctypes.data)
+    if rc == -10001:
+        raise ValueError("socket table: af must be 4 or 6, connected 0 or 1, every tuple distinct")
+    _check("wc_rx_socktab_build", rc)
+    return tab.view(np.uint8)
+
+
+def _addr_bytes(af: int, addr) -> np.ndarray:
+    a = np.zeros(16, dtype=np.uint8)
+    b = np.frombuffer(bytes(addr), dtype=np.uint8)
+    if b.size < (4 if af == 4 else 16):
+        raise ValueError("an IPv4 address is 4 bytes, an IPv6 address 16")
+    a[:min(b.size, 16)] = b[:16]
+    return a
+
+
+def rx_socktab_lookup(tab: np.ndarray, af: int, laddr, lport: int, raddr, rport: int) -> int:
+    """The table's own lookup on the host (wc_rx_socktab_lookup): the connected
+    tuple first, then the bound one; the socket's index or RX_SOCK_UNBOUND."""
+    tab = np.ascontiguousarray(tab).view(np.uint8)
+    la, ra = _addr_bytes(af, laddr), _addr_bytes(af, raddr)
+    return int(_lib.active().wc_rx_socktab_lookup(tab.ctypes.data, int(af), la.ctypes.data,
+                                                  int(lport), ra.ctypes.data, int(rport)))
+
+
+def rx_demux_scratch(n: int) -> int:
+    """Bytes of device scratch wc_rx_demux needs for n frames (no GPU)."""
+    return int(_lib.active().wc_rx_demux_scratch(int(n)))
+
+
+def rx_demux(base: torch.Tensor, offsets: torch.Tensor, records: torch.Tensor,
+             table: torch.Tensor, ns: int, want_list: bool = True, stream=None,
+             out_list: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """The socket of every delivered frame and the per-socket index lists
+    (wc_rx_demux), behind an rx_deliver_ragged of the same frames whose
+    ``records`` it reads; ``table``: rx_socktab_build's bytes for ``ns``
+    sockets as a device tensor.  Returns ``(sock uint8, list, start)``: socket
+    ``s``'s frames are ``list[start[s]:start[s + 1]]`` for ``s < 254``, the
+    unbound ones ``list[start[254]:start[255]]``, ``start`` a 256-entry int64
+    device tensor (None, None with ``want_list=False``).  Asynchronous; the
+    scratch is allocated here unless given -- give one per call in flight when
+    ``stream`` is not the current stream, so that it outlives the launches."""
+    _same_device(base, offsets=offsets, records=records, table=table)
+    n = offsets.numel()
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    if offsets.element_size() != 8 or not offsets.is_contiguous() or not base.is_contiguous():
+        raise ValueError("offsets must be contiguous 8-byte integers, base contiguous")
+    if _nbytes(records) != n * RX_RECORD.itemsize or not records.is_contiguous():
+        raise ValueError("records must be the contiguous (n, 16) bytes of rx_deliver_ragged")
+    if not 0 <= int(ns) <= RX_DEMUX_MAX_SOCKS:
+        raise ValueError(f"ns must be 0..{RX_DEMUX_MAX_SOCKS}")
+    if not table.is_contiguous() or _nbytes(table) < rx_socktab_bytes(ns):
+        raise ValueError("table must hold the rx_socktab_build bytes of ns sockets")
+    d = base.device
+    sock = torch.empty(n, dtype=torch.uint8, device=d)
+    lst = start = None
+    if want_list:
+        own = out_list is None
+        lst = torch.empty(max(n, 1), dtype=torch.uint32, device=d) if own else out_list
+        if lst.numel() < max(n, 1) or lst.element_size() != 4 or not lst.is_contiguous() \
+                or lst.device != d:
+            raise ValueError(f"out_list must be a contiguous 4-byte tensor of >= max(n, 1) "
+                             f"entries on {d}")
+        start = torch.zeros(_RX_STARTS, dtype=torch.int64, device=d)
+        if scratch is None:
+            scratch = torch.empty(max(1, (rx_demux_scratch(n) + 3) // 4), dtype=torch.int32,
+                                  device=d)
+        elif _nbytes(scratch) < rx_demux_scratch(n) or scratch.device != d:
+            raise ValueError(f"scratch must hold rx_demux_scratch(n) bytes on {d}")
+    with _on_device(d):
+        _check("wc_rx_demux", _lib.active().wc_rx_demux(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(records), n, _dev_ptr(table), int(ns),
+            sock.data_ptr() if n else None, lst.data_ptr() if want_list else None,
+            start.data_ptr() if want_list else None,
+            scratch.data_ptr() if want_list else None, _stream_ptr(stream, d)))
+    if want_list and own:
+        lst = lst[:n]
+    return sock, lst, start
+
+
+def rx_demux_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray,
+                  tab: np.ndarray, ns: int):
+    """rx_deliver_host plus the demultiplex (wc_rx_demux_host, synchronous):
+    ``(uint8 verdicts, RX_RECORD records, uint8 socket ids, uint32 list,
+    uint64 start[256], drop count)``; ``tab``: rx_socktab_build's bytes for
+    ``ns`` sockets."""
+    buf, off, lens = _host_batch_args(buf, offsets, frame_lens)
+    n = off.size
+    tab = np.ascontiguousarray(tab).view(np.uint8)
+    if tab.size < rx_socktab_bytes(ns) or tab.ctypes.data % 4:
+        raise ValueError("tab must hold the 4-byte-aligned rx_socktab_build bytes of ns sockets")
+    verdicts = np.empty(n, dtype=np.uint8)
+    records = np.zeros(n, dtype=RX_RECORD)
+    sock = np.empty(n, dtype=np.uint8)
+    lst = np.empty(max(n, 1), dtype=np.uint32)  # (never empty: its pointer must not be NULL)
+    start = np.empty(_RX_STARTS, dtype=np.uint64)
+    drops = ctypes.c_uint64()
+    _check("wc_rx_demux_host", _lib.active().wc_rx_demux_host(
+        buf.ctypes.data, buf.size, off.ctypes.data, lens.ctypes.data, n, tab.ctypes.data, int(ns),
+        verdicts.ctypes.data, records.ctypes.data, sock.ctypes.data, lst.ctypes.data,
+        start.ctypes.data, ctypes.byref(drops)))
+    return verdicts, records, sock, lst[:int(start[-1])].copy(), start, int(drops.value)
+
+
+# --------------------------------------------------------------------------
 # TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
 
 # enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)

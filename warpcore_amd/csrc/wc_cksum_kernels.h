@@ -192,6 +192,19 @@ uint64_t rxsel_scratch_bytes(uint64_t n);
 hipError_t launch_rx_select(const uint8_t *verdict, uint64_t n, uint32_t mask, uint32_t *list,
                             uint64_t *count, void *scratch, hipStream_t st);
 
+// RX socket demultiplex (wc_k_rxdemux.hip) behind a DELIVER launch over the
+// same frames: sock[i] = the index of the socket frame i's record and address
+// bytes select in `table` (a wc_rx_socktab_build blob of `ns` sockets, device
+// memory), 0xFF for a delivered frame without one, 0xFE for rec[i].af == 0.
+// With `list`: the delivered frames' indices grouped by socket, the unbound
+// ones last, each group ascending, and start[256] (wc_cksum.h); `scratch`:
+// rxdemux_scratch_bytes(n) bytes, 4-byte aligned.  One launch, or three with
+// the list.  1 <= n <= 2^32, ns <= 254.
+uint64_t rxdemux_scratch_bytes(uint64_t n);
+hipError_t launch_rx_demux(const void *base, const uint64_t *offs, const void *rec, uint64_t n,
+                           const void *table, uint32_t ns, uint8_t *sock, uint32_t *list,
+                           uint64_t *start, void *scratch, hipStream_t st);
+
 // TX seal of Ethernet frames [base + offs[i], + flens[i]) (wc_k_tx.hip): both
 // checksums computed with their fields taken as 0 and stored raw into the
 // frame, status[i] its enum wc_tx_status code; out_ip / out_udp (optional)

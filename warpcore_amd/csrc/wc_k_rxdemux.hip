@@ -1,0 +1,360 @@
+// wc_k_rxdemux.hip -- wc_rx_demux on gfx950: the socket every delivered frame
+// belongs to (udp_rx's two w_get_sock calls, udp.c:141-156) and the delivered
+// frames' indices grouped by socket, each group in ring order (DESIGN.md
+// section 8, row 7).
+//
+// Three launches on the caller's stream, in wc_k_rxsel.hip's style: their
+// order on the stream is the only ordering between the phases, no workgroup
+// waits for another, no global atomic, and the output does not depend on how
+// the workgroups are scheduled:
+//   1. k_rxdemux_key      one lane per frame: its 16-byte record (coalesced);
+//                         where af != 0 the aligned 16-byte chunks that
+//                         overlap the two addresses (8 bytes at 14 + 12 for
+//                         IPv4: up to two chunks; 32 bytes at 14 + 8 for
+//                         IPv6: up to three), the probe of the table's LDS
+//                         copy, sock[i]; and block b's count of every class
+//                         into counts[class][b] (class-major);
+//   2. k_rxdemux_scan     ONE workgroup: the exclusive scan of the
+//                         (ns + 1) x nblocks counts in place -- class-major,
+//                         so a scanned count is already the block's first
+//                         position in the list -- and the 256 start entries;
+//   3. k_rxdemux_scatter  block b reads its sock bytes again, ranks them the
+//                         same way, puts the indices class by class into LDS
+//                         and writes each class's run as one contiguous store.
+// A block is kDmxBlock = 4096 frames, wave w of its sixteen takes the 256
+// frames from 256 w on, 64 at a time, so (wave, step, lane) order is ring
+// order; the key kernel has a wave's four steps' loads in flight together.
+// A lane's rank among the lanes of its class in one step comes from ballots
+// over the 8 id bits; the classes' running counts are per wave in LDS,
+// added to by one lane per class and step -- nothing is ordered by an atomic.
+// Classes: socket ids 0 .. ns - 1, then "unbound" (id 0xFF, row ns); id 0xFE
+// (no record) and anything else a sock byte might hold belong to none.
+#include "wc_device.h"
+#include "wc_rx_socktab.h"
+
+namespace wc {
+namespace {
+
+constexpr int kDmxThreads = 1024;
+constexpr int kDmxWaves = kDmxThreads / 64;
+constexpr int kDmxSteps = 4;                                  // 64-frame steps per wave
+constexpr uint32_t kDmxWaveFrames = 64u * kDmxSteps;          // 256
+constexpr uint32_t kDmxBlock = kDmxWaveFrames * kDmxWaves;    // 4096 frames per block
+constexpr int kDmxScan = 1024;                                // threads of the scan workgroup
+constexpr int kDmxScanPer = 4;                                // counts per thread and iteration
+constexpr uint32_t kSockNone = 0xFEu, kSockUnbound = 0xFFu;   // WC_RX_SOCK_*
+constexpr uint32_t kDmxStarts = 256;
+
+// The lanes of this wave whose id equals this lane's, among those with
+// `counted` (0 for a lane without it).  Every lane of the wave calls it.
+__device__ __forceinline__ uint64_t class_peers(uint32_t id, bool counted)
+{
+    uint64_t m = __ballot(counted);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (id >> b) & 1u;
+        const uint64_t set = __ballot(bit);
+        m &= bit ? set : ~set;
+    }
+    return counted ? m : 0ull;
+}
+
+__device__ __forceinline__ bool class_counted(uint32_t id, uint32_t ns)
+{
+    return id < ns || id == kSockUnbound;
+}
+
+// One step of a wave's ranking: this lane's rank among the lanes of its class
+// so far in the wave (run[id] before the step plus the peers below it), and
+// the class's running count moved on by one lane.  run: this wave's 256
+// counters in LDS; the wave's own LDS operations execute in order.
+__device__ __forceinline__ uint32_t class_rank(uint32_t *run, uint32_t id, bool counted)
+{
+    const uint64_t peers = class_peers(id, counted);
+    const uint32_t below = mbcnt64(peers);
+    uint32_t r = 0;
+    if (counted)
+        r = run[id] + below;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (counted && below == 0u)
+        run[id] = r + (uint32_t)__builtin_popcountll(peers);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return r;
+}
+
+// Bytes [s, s + 32) of the 48-byte window w[0 .. 12) as eight dwords (s < 16).
+__device__ __forceinline__ void window_bytes(uint32_t w[13], uint32_t s, uint32_t d[8])
+{
+    w[12] = 0u;
+    if (s & 4u) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            w[k] = w[k + 1];
+    }
+    if (s & 8u) {
+#pragma unroll
+        for (int k = 0; k < 11; ++k)
+            w[k] = w[k + 2];
+    }
+    const uint32_t sh = 8u * (s & 3u);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        d[k] = (uint32_t)((((uint64_t)w[k + 1] << 32) | w[k]) >> sh);
+}
+
+// The socket id of the frame at `frame` with record words r (af != 0): both
+// addresses through the aligned chunks that overlap them -- `last` is the
+// chunk of their last byte, never passed, so an IPv4 frame's loads end with
+// its destination address --, then the table's two-step lookup.
+__device__ __forceinline__ uint32_t frame_sock(uint64_t frame, const u32x4 &r,
+                                               const uint32_t *slots, uint32_t nslots)
+{
+    const uint32_t af = r.z & 0xFFu;
+    const bool v4 = af == 4u;
+    const uint64_t at = frame + (v4 ? 14u + 12u : 14u + 8u);
+    const uint64_t first = at & ~15ull, last = (at + (v4 ? 7u : 31u)) & ~15ull;
+    const u32x4 c0 = load_chunk<false>(first);
+    const u32x4 c1 = load_chunk<false>(first + 16u < last ? first + 16u : last);
+    const u32x4 c2 = load_chunk<false>(last);
+    uint32_t w[13] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, 0u};
+    uint32_t d[8];
+    window_bytes(w, (uint32_t)(at & 15u), d);
+    // IPv4: src, dst = d[0], d[1]; IPv6: src = d[0..3], dst = d[4..7]
+    uint32_t l[4], rm[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        l[j] = v4 ? d[1] : d[4 + j];
+        rm[j] = d[j];
+    }
+    uint32_t k[tab::kTabKeyWords];
+    tab::tab_key(k, af, 1u, r.y >> 16, r.y & 0xFFFFu, l, rm); // local = dport, remote = sport
+    return tab::tab_lookup(slots, nslots, k);
+}
+
+// LDS of the key kernel (all dynamic, 16-byte aligned): the waves' class
+// counters, then the table's slots.
+constexpr uint32_t kDmxRunWords = kDmxWaves * 256u;
+
+__global__ void __launch_bounds__(kDmxThreads)
+k_rxdemux_key(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
+              const u32x4 *__restrict__ rec, uint64_t n, const uint32_t *__restrict__ table,
+              uint32_t ns, uint32_t nslots, uint8_t *__restrict__ sock,
+              uint32_t *__restrict__ counts, uint32_t nblocks)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t *const run_all = lds, *const slots = lds + kDmxRunWords;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t k = threadIdx.x; k < kDmxRunWords; k += kDmxThreads)
+        run_all[k] = 0u;
+    const uint32_t tw = tab::kTabSlotWords * nslots;
+    for (uint32_t k = threadIdx.x; k < tw; k += kDmxThreads)
+        slots[k] = table[tab::kTabHeaderWords + k];
+    __syncthreads();
+    uint32_t *const run = run_all + 256u * wave;
+    const uint64_t w0 = (uint64_t)blockIdx.x * kDmxBlock + (uint64_t)wave * kDmxWaveFrames;
+    // the ids of the wave's steps first (their loads independent of each
+    // other), then the stores and the ranking
+    uint32_t ids[kDmxSteps];
+#pragma unroll
+    for (int step = 0; step < kDmxSteps; ++step) {
+        const uint64_t i = w0 + 64u * step + lane;
+        uint32_t id = kSockNone;
+        if (i < n) {
+            const u32x4 r = rec[i];
+            if (r.z & 0xFFu) {
+                id = frame_sock((uint64_t)(uintptr_t)base + offs[i], r, slots, nslots);
+                id = class_counted(id, ns) ? id : kSockUnbound; // (a table of another ns)
+            }
+        }
+        ids[step] = id;
+    }
+#pragma unroll
+    for (int step = 0; step < kDmxSteps; ++step) {
+        const uint64_t i = w0 + 64u * step + lane;
+        if (i < n)
+            sock[i] = (uint8_t)ids[step];
+        if (counts)
+            (void)class_rank(run, ids[step], ids[step] != kSockNone);
+    }
+    if (!counts)
+        return;
+    __syncthreads();
+    const uint32_t c = threadIdx.x; // the first 256 threads: one id each
+    if (c < 256u && class_counted(c, ns)) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kDmxWaves; ++w)
+            t += run_all[256u * w + c];
+        counts[(size_t)(c < ns ? c : ns) * nblocks + blockIdx.x] = t;
+    }
+}
+
+// counts[0 .. (ns + 1) * nblocks) -> exclusive offsets, in place (a 64-bit
+// running total: only the grand total may reach 2^32); start[s] = row s's
+// first offset for s < ns, the unbound row's for ns <= s <= 254, the total
+// for s = 255.
+__global__ void __launch_bounds__(kDmxScan)
+k_rxdemux_scan(uint32_t *__restrict__ counts, uint32_t nblocks, uint32_t ns,
+               unsigned long long *__restrict__ start)
+{
+    __shared__ uint32_t ws[kDmxScan / 64];
+    __shared__ unsigned long long unbound;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t total = (ns + 1u) * nblocks; // <= 255 * 2^20
+    uint64_t carry = 0; // the same in every thread
+    for (uint32_t at = 0; at < total; at += kDmxScan * kDmxScanPer) {
+        const uint32_t i0 = at + kDmxScanPer * threadIdx.x; // this thread's run of counts
+        uint32_t v[kDmxScanPer], sum = 0;
+#pragma unroll
+        for (int k = 0; k < kDmxScanPer; ++k) {
+            v[k] = i0 + k < total ? counts[i0 + k] : 0u;
+            sum += v[k];
+        }
+        const uint32_t incl = wave_incl_sum(sum);
+        if (lane == 63)
+            ws[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0; // (<= 4096 counts of <= 4096 frames each: no wrap)
+#pragma unroll
+        for (int w = 0; w < kDmxScan / 64; ++w) {
+            const uint32_t t = ws[w];
+            before += w < wave ? t : 0u;
+            all += t;
+        }
+        uint64_t excl = carry + before + incl - sum;
+#pragma unroll
+        for (int k = 0; k < kDmxScanPer; ++k) {
+            const uint32_t i = i0 + k;
+            if (i < total) {
+                counts[i] = (uint32_t)excl;
+                const uint32_t row = i / nblocks;
+                if (i == row * nblocks) {
+                    if (row < ns)
+                        start[row] = excl;
+                    else
+                        unbound = excl;
+                }
+            }
+            excl += v[k];
+        }
+        carry += all;
+        __syncthreads(); // ws is rewritten by the next iteration
+    }
+    if (threadIdx.x >= ns && threadIdx.x < kDmxStarts - 1u)
+        start[threadIdx.x] = unbound;
+    if (threadIdx.x == kDmxStarts - 1u)
+        start[threadIdx.x] = carry;
+}
+
+__global__ void __launch_bounds__(kDmxThreads)
+k_rxdemux_scatter(const uint8_t *__restrict__ sock, uint64_t n, uint32_t ns,
+                  const uint32_t *__restrict__ offsets, uint32_t nblocks,
+                  uint32_t *__restrict__ list)
+{
+    __shared__ uint32_t run_all[kDmxRunWords];
+    __shared__ uint32_t idx[kDmxBlock];
+    __shared__ uint8_t cls[kDmxBlock];
+    __shared__ uint32_t lbase[256], goff[256];
+    __shared__ uint32_t ws[kDmxWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t k = threadIdx.x; k < kDmxRunWords; k += kDmxThreads)
+        run_all[k] = 0u;
+    __syncthreads();
+    uint32_t *const run = run_all + 256u * wave;
+    const uint64_t w0 = (uint64_t)blockIdx.x * kDmxBlock + (uint64_t)wave * kDmxWaveFrames;
+    // pass 1: the waves' class totals, as the key kernel counted them
+    uint32_t ids[kDmxSteps];
+#pragma unroll
+    for (int step = 0; step < kDmxSteps; ++step) {
+        const uint64_t i = w0 + 64u * step + lane;
+        const uint32_t id = i < n ? (uint32_t)sock[i] : kSockNone;
+        ids[step] = id;
+        (void)class_rank(run, id, class_counted(id, ns));
+    }
+    __syncthreads();
+    // class c's place among the block's indices in LDS (classes ascending:
+    // the sockets, then 0xFF) and in the list; each wave's counters restart at
+    // the first LDS position of its frames of the class
+    const uint32_t c = threadIdx.x; // the first 256 threads: one id each
+    const bool own = c < 256u;
+    uint32_t tot = 0;
+    if (own) {
+        for (int w = 0; w < kDmxWaves; ++w)
+            tot += run_all[256u * w + c];
+    }
+    const uint32_t incl = wave_incl_sum(tot);
+    if (lane == 63)
+        ws[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kDmxWaves; ++w) {
+        const uint32_t x = ws[w];
+        before += w < wave ? x : 0u;
+        total += x;
+    }
+    if (own) {
+        uint32_t at = before + incl - tot;
+        lbase[c] = at;
+        goff[c] = class_counted(c, ns) ? offsets[(size_t)(c < ns ? c : ns) * nblocks + blockIdx.x]
+                                       : 0u;
+        for (int w = 0; w < kDmxWaves; ++w) {
+            const uint32_t t = run_all[256u * w + c];
+            run_all[256u * w + c] = at;
+            at += t;
+        }
+    }
+    __syncthreads();
+    // pass 2: every counted frame's index to its place (< total <= kDmxBlock)
+#pragma unroll
+    for (int step = 0; step < kDmxSteps; ++step) {
+        const uint32_t id = ids[step];
+        const bool counted = class_counted(id, ns);
+        const uint32_t p = class_rank(run, id, counted);
+        if (counted && p < kDmxBlock) {
+            idx[p] = (uint32_t)(w0 + 64u * step + lane);
+            cls[p] = (uint8_t)id;
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < total; k += kDmxThreads) {
+        const uint32_t id = cls[k];
+        const uint64_t to = (uint64_t)goff[id] + (k - lbase[id]);
+        if (to < n) // (always, while sock holds what the key kernel counted)
+            list[to] = idx[k];
+    }
+}
+
+} // namespace
+
+uint64_t rxdemux_scratch_bytes(uint64_t n)
+{
+    if (n == 0)
+        return 0;
+    const uint64_t nblocks = (n - 1u) / kDmxBlock + 1u;
+    return 4u * (uint64_t)(tab::kTabMaxSocks + 1u) * nblocks;
+}
+
+hipError_t launch_rx_demux(const void *base, const uint64_t *offs, const void *rec, uint64_t n,
+                           const void *table, uint32_t ns, uint8_t *sock, uint32_t *list,
+                           uint64_t *start, void *scratch, hipStream_t st)
+{
+    const uint32_t nblocks = (uint32_t)((n - 1u) / kDmxBlock + 1u); // <= 2^20
+    const uint32_t nslots = tab::tab_slots(ns);
+    const size_t lds = 4u * (kDmxRunWords + (size_t)tab::kTabSlotWords * nslots); // <= 40 KiB
+    uint32_t *counts = list ? (uint32_t *)scratch : nullptr;
+    hipLaunchKernelGGL(k_rxdemux_key, dim3(nblocks), dim3(kDmxThreads), lds, st,
+                       (const uint8_t *)base, offs, (const u32x4 *)rec, n, (const uint32_t *)table,
+                       ns, nslots, sock, counts, nblocks);
+    if (list) {
+        hipLaunchKernelGGL(k_rxdemux_scan, dim3(1), dim3(kDmxScan), 0, st, counts, nblocks, ns,
+                           (unsigned long long *)start);
+        hipLaunchKernelGGL(k_rxdemux_scatter, dim3(nblocks), dim3(kDmxThreads), 0, st,
+                           (const uint8_t *)sock, n, ns, (const uint32_t *)counts, nblocks, list);
+    }
+    return hipGetLastError();
+}
+
+} // namespace wc

@@ -53,6 +53,11 @@ constexpr bool kind_is_tx(int kind) { return kind == kKindTx || kind == kKindTxZ
 // struct wc_rx_record of every frame into the second array.  Never the
 // resident server's (a server result slot is 32 bits).
 constexpr int kKindRxDeliver = 6;
+// RX demultiplex (wc_rx_demux_host): the deliver kind's two arrays, and behind
+// the DELIVER kernel the demux key kernel's 1-byte socket ids into the third
+// (against the table staged in Device::d_socktab).  Never the server's.
+constexpr int kKindRxDemux = 7;
+constexpr bool kind_has_rec(int kind) { return kind == kKindRxDeliver || kind == kKindRxDemux; }
 
 // Small batches over registered memory skip the copy engines: the kernel
 // reads the packets straight out of the page-locked region over PCIe, and
@@ -80,16 +85,18 @@ constexpr OutRow out_row(int kind)
            : kind == kKindFused ? OutRow{{2, 2, 0}}
            : kind_is_tx(kind)   ? OutRow{{2, 2, 1}}
            : kind == kKindRxDeliver ? OutRow{{1, 16, 0}}
+           : kind == kKindRxDemux ? OutRow{{1, 16, 1}}
                                 : OutRow{{2, 0, 0}};
 }
 static_assert(out_row(WC_CKSUM_IP).is(2, 0, 0) && out_row(WC_CKSUM_PAYLOAD).is(2, 0, 0), "");
 static_assert(out_row(kKindRx).is(1, 0, 0) && out_row(kKindFused).is(2, 2, 0), "");
 static_assert(out_row(kKindTx).is(2, 2, 1) && out_row(kKindTxZero).is(2, 2, 1), "");
-static_assert(out_row(kKindRxDeliver).is(1, 16, 0), "");
-// The widest row every buffer set holds from its creation.  The deliver
-// kind's 16-byte records are not under it: a set allocates that array of its
-// own at its first deliver batch (BufSet::need), so a process that never
-// delivers pins what it did before.
+static_assert(out_row(kKindRxDeliver).is(1, 16, 0) && out_row(kKindRxDemux).is(1, 16, 1), "");
+// The widest row every buffer set holds from its creation.  The deliver and
+// demux kinds' 16-byte records are not under it: a set allocates that array
+// of its own at its first such batch (BufSet::need), so a process that never
+// delivers pins what it did before; the demux kind's socket ids fit the third
+// array as it is.
 constexpr OutRow kOutCap = out_row(kKindTx);
 
 // The caller's result arrays of a host batch, in out_row's order.
@@ -109,7 +116,7 @@ struct BufView {
     // Result array k of a batch of `kind`.
     uint8_t *out_of(int kind, int k) const
     {
-        return kind == kKindRxDeliver && k == 1 ? rec : out[k];
+        return kind_has_rec(kind) && k == 1 ? rec : out[k];
     }
 };
 struct BufSet {
@@ -118,7 +125,7 @@ struct BufSet {
     uint64_t pkts = 0;
     int alloc(uint64_t pkts, bool mapped_pinned);
     // Before a batch of `kind` uses the set: the record array at the first
-    // deliver batch, nothing otherwise.
+    // deliver or demux batch, nothing otherwise.
     int need(int kind);
     void free(); // (safe on a partly built set)
     // Packets [0, n)'s results of `kind` to the caller's arrays at packet lo.
@@ -212,6 +219,11 @@ struct Device {
     uint32_t rx_gen = 0;
     bool rx_early = false;
     uint32_t rx_nlaunch[2] = {}, rx_ndecided = 0; // WC_RX_TRACE=2 counts
+    // wc_rx_demux_host: the device copy of the call's socket table (allocated
+    // at the first demux call, for the largest table) and its socket count,
+    // staged under g_mu before the call's first launch.
+    void *d_socktab = nullptr;
+    uint32_t socktab_ns = 0;
 };
 constexpr int kRxSets = 4;
 extern std::mutex g_rx_mu; // rx_launch's tally bookkeeping (batch calls run outside g_mu)
@@ -408,8 +420,10 @@ int host_zero_copy(Device &D, const uint8_t *dbase, const uint64_t *h_off,
 // A host-memory batch on the current device by the rules of wc_cksum_host
 // (server, zero-copy launch, zero-copy stream or pipeline); outs: every
 // array out_row(kind) uses.
+// h_tab / ns: the socket table of a kKindRxDemux batch (host memory).
 int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
-               const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind);
+               const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind,
+               const void *h_tab = nullptr, uint32_t ns = 0);
 // Every packet of a host batch inside [0, h_bytes); whether the offsets
 // ascend, the bytes the packets' checks read, and (optional) the byte range
 // they span.

@@ -263,6 +263,7 @@ int wc_gpu_fini(void)
         std::lock_guard<std::mutex> lr(g_rx_mu);
         for (int k = 0; k < kRxSets; ++k)
             (void)hipHostFree(D.h_rx_tally[k]);
+        (void)hipFree(D.d_socktab);
         (void)hipStreamDestroy(D.scalar_st);
         (void)hipHostFree(D.h_stage);
         (void)hipHostFree(D.h_res);

@@ -1,5 +1,6 @@
 // wc_rt_host.cpp -- host-memory batches (wc_cksum_host, wc_cksum_ip_udp_host,
-// wc_rx_verdict_host, wc_rx_deliver_host, the seal's compute pass, wc_host_register): the
+// wc_rx_verdict_host, wc_rx_deliver_host, wc_rx_demux_host, the seal's compute pass,
+// wc_host_register): the
 // resident server or one zero-copy launch for a small registered batch, else
 // the in-place stream or the pipelined path (hipMemcpyAsync H2D, kernel, D2H)
 // through pinned staging.  All three launch paths keep their per-batch arrays
@@ -7,6 +8,7 @@
 // drain), and pick a kind's result arrays from out_row (wc_rt.h).
 
 #include "wc_rt.h"
+#include "wc_rx_socktab.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -48,7 +50,7 @@ int BufSet::alloc(uint64_t pkts, bool mapped_pinned)
 
 int BufSet::need(int kind)
 {
-    if (kind != kKindRxDeliver || h.rec)
+    if (!kind_has_rec(kind) || h.rec)
         return WC_OK;
     if (buf_alloc(mapped, h.rec, d.rec, pkts * out_row(kKindRxDeliver).w[1]))
         return WC_OK;
@@ -229,6 +231,13 @@ int run_ragged_any(Device &D, const Config &C, const uint8_t *d_base, const BufV
         return hip_err(rx_launch(D, C, d_base, b.off, b.len, n, b.out[0], nullptr, st));
     if (kind == kKindRxDeliver)
         return hip_err(rx_launch(D, C, d_base, b.off, b.len, n, b.out[0], nullptr, st, b.rec));
+    if (kind == kKindRxDemux) { // the key kernel behind the DELIVER kernel: ids, no list
+        hipError_t e = rx_launch(D, C, d_base, b.off, b.len, n, b.out[0], nullptr, st, b.rec);
+        if (e == hipSuccess)
+            e = wc::launch_rx_demux(d_base, b.off, b.rec, n, D.d_socktab, D.socktab_ns, b.out[2],
+                                    nullptr, nullptr, nullptr, st);
+        return hip_err(e);
+    }
     if (kind_is_tx(kind)) // compute only: the calling thread makes the stores (wc_rt_tx.cpp)
         return hip_err(wc::launch_tx_seal(
             const_cast<uint8_t *>(d_base), b.off, b.len, n,
@@ -615,7 +624,8 @@ int host_pipeline(Device &D, const HostBatch &b, uint64_t n)
 // server or one zero-copy launch for a small registered batch, else the
 // in-place stream or the pipeline.
 int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
-               const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind)
+               const uint16_t *h_len, uint64_t n, const HostOuts &outs, int kind,
+               const void *h_tab, uint32_t ns)
 {
     if (n == 0)
         return WC_OK;
@@ -638,8 +648,22 @@ int host_batch(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
     int rc = init_locked(-1, &D);
     if (rc)
         return rc;
+    if (kind == kKindRxDemux) {
+        // The table, once per call: no launch of an earlier call is in flight
+        // (host calls are synchronous and hold g_mu).
+        const uint64_t cap = 4ull * wc::tab::tab_words(wc::tab::kTabMaxSocks);
+        if (!D->d_socktab && hipMalloc(&D->d_socktab, cap) != hipSuccess) {
+            D->d_socktab = nullptr;
+            return WC_ENOMEM;
+        }
+        rc = hip_err(hipMemcpy(D->d_socktab, h_tab, 4ull * wc::tab::tab_words(ns),
+                               hipMemcpyHostToDevice));
+        if (rc)
+            return rc;
+        D->socktab_ns = ns;
+    }
     const uint8_t *dbase = registered_dptr_locked(h_base, h_bytes);
-    if (dbase && !kind_is_tx(kind) && kind != kKindRxDeliver && g_cfg.serve &&
+    if (dbase && !kind_is_tx(kind) && !kind_has_rec(kind) && g_cfg.serve &&
         server_enabled_locked() &&
         n <= (uint64_t)g_cfg.serve_max) {
         bool fits = true; // (a fused header adds at most 40 bytes to the span)

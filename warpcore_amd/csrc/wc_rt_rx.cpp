@@ -1,9 +1,12 @@
 // wc_rt_rx.cpp -- RX verdict launches (wc_rx_verdict_ragged, wc_rx_deliver_ragged
 // and the host paths' RX batches): the default ADAPT mode picks EARLY or HT
 // per launch from the tallies earlier launches' tiles stored; and
-// wc_rx_select, the index lists over the verdict bytes.
+// wc_rx_select, the index lists over the verdict bytes; and the socket
+// demultiplex behind delivery -- the table's host side (wc_rx_socktab_*),
+// wc_rx_demux and wc_rx_demux_host.
 
 #include "wc_rt.h"
+#include "wc_rx_socktab.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -101,6 +104,7 @@ hipError_t rx_launch(Device &D, const Config &C, const void *base, const uint64_
 } // namespace wc
 
 using namespace wc::rt;
+namespace tab = wc::tab;
 
 extern "C" {
 
@@ -219,6 +223,170 @@ int wc_rx_deliver_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
         *h_count = cnt;
     if (h_drops)
         *h_drops = drops;
+    return WC_OK;
+}
+
+// --- RX socket demultiplex ---------------------------------------------------
+
+uint64_t wc_rx_socktab_bytes(uint32_t ns)
+{
+    // (past the largest table: still its size, so the function never decreases)
+    return 4ull * tab::tab_words(std::min<uint32_t>(ns, tab::kTabMaxSocks));
+}
+
+// A socket's canonical key: its own bytes with the ignored ones dropped.
+static void sock_key(const struct wc_rx_sock &s, uint32_t k[tab::kTabKeyWords])
+{
+    uint32_t l[4], r[4];
+    memcpy(l, s.laddr, 16);
+    memcpy(r, s.raddr, 16);
+    tab::tab_key(k, s.af, s.connected, s.lport, s.rport, l, r);
+}
+
+int wc_rx_socktab_build(const struct wc_rx_sock *socks, uint32_t ns, void *h_tab)
+{
+    static_assert(sizeof(struct wc_rx_sock) == 4 * tab::kTabKeyWords, "the key is the struct");
+    static_assert(WC_RX_DEMUX_MAX_SOCKS == tab::kTabMaxSocks && WC_RX_SOCK_UNBOUND == tab::kTabUnbound,
+                  "header and table agree");
+    if (ns > tab::kTabMaxSocks || !h_tab || ((uintptr_t)h_tab & 3u) || (ns && !socks))
+        return WC_EINVAL;
+    for (uint32_t i = 0; i < ns; ++i)
+        if ((socks[i].af != 4 && socks[i].af != 6) || socks[i].connected > 1)
+            return WC_EINVAL;
+    uint32_t *const t = (uint32_t *)h_tab, *const slot = t + tab::kTabHeaderWords;
+    const uint32_t nslots = tab::tab_slots(ns);
+    t[0] = tab::kTabMagic, t[1] = nslots, t[2] = ns, t[3] = 0u;
+    for (uint32_t q = 0; q < nslots; ++q) {
+        uint32_t *const s = slot + q * tab::kTabSlotWords;
+        std::fill(s, s + tab::kTabSlotWords, 0u);
+        s[tab::kTabKeyWords] = tab::kTabEmpty;
+    }
+    for (uint32_t i = 0; i < ns; ++i) { // in the caller's order: the same input, the same bytes
+        uint32_t k[tab::kTabKeyWords];
+        sock_key(socks[i], k);
+        uint32_t at = tab::tab_hash(k) & (nslots - 1u);
+        while (slot[at * tab::kTabSlotWords + tab::kTabKeyWords] != tab::kTabEmpty) {
+            if (!memcmp(slot + at * tab::kTabSlotWords, k, sizeof k))
+                return WC_EINVAL; // the same tuple twice
+            at = (at + 1u) & (nslots - 1u);
+        }
+        memcpy(slot + at * tab::kTabSlotWords, k, sizeof k);
+        slot[at * tab::kTabSlotWords + tab::kTabKeyWords] = i;
+    }
+    return WC_OK;
+}
+
+// Whether h_tab starts like a blob of wc_rx_socktab_build (for `ns` sockets,
+// where the caller names a count).
+static bool socktab_ok(const void *h_tab, const uint32_t *ns)
+{
+    if (!h_tab || ((uintptr_t)h_tab & 3u))
+        return false;
+    const uint32_t *t = (const uint32_t *)h_tab;
+    return t[0] == tab::kTabMagic && t[2] <= tab::kTabMaxSocks && t[1] == tab::tab_slots(t[2]) &&
+           (!ns || *ns == t[2]);
+}
+
+uint8_t wc_rx_socktab_lookup(const void *h_tab, uint8_t af, const uint8_t *laddr, uint16_t lport,
+                             const uint8_t *raddr, uint16_t rport)
+{
+    if (!socktab_ok(h_tab, nullptr) || (af != 4 && af != 6) || !laddr || !raddr)
+        return WC_RX_SOCK_UNBOUND;
+    uint32_t l[4] = {}, r[4] = {}, k[tab::kTabKeyWords];
+    memcpy(l, laddr, af == 4 ? 4 : 16);
+    memcpy(r, raddr, af == 4 ? 4 : 16);
+    tab::tab_key(k, af, 1u, lport, rport, l, r);
+    const uint32_t *t = (const uint32_t *)h_tab;
+    return (uint8_t)tab::tab_lookup(t + tab::kTabHeaderWords, t[1], k);
+}
+
+uint64_t wc_rx_demux_scratch(uint64_t n)
+{
+    return wc::rxdemux_scratch_bytes(n);
+}
+
+static constexpr uint64_t kRxStarts = 256; // entries of d_start / h_start
+
+int wc_rx_demux(const void *d_base, const uint64_t *d_off, const struct wc_rx_record *d_rec,
+                uint64_t n, const void *d_tab, uint32_t ns, uint8_t *d_sock, uint32_t *d_list,
+                uint64_t *d_start, void *d_scratch, void *stream)
+{
+    if (n > kRxSelectMax || ns > tab::kTabMaxSocks || (d_list != nullptr) != (d_start != nullptr))
+        return WC_EINVAL;
+    if (n == 0) {
+        if (!d_start)
+            return WC_OK;
+        Device *D = nullptr;
+        Config C;
+        const int rc = ensure_device(&D, &C);
+        if (rc)
+            return rc;
+        return hip_err(hipMemsetAsync(d_start, 0, kRxStarts * sizeof(uint64_t),
+                                      (hipStream_t)stream));
+    }
+    if (!d_base || !d_off || !d_rec || ((uintptr_t)d_rec & 15u) || !d_tab ||
+        ((uintptr_t)d_tab & 3u) || !d_sock)
+        return WC_EINVAL;
+    if (d_list && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
+        return WC_EINVAL;
+    Device *D = nullptr;
+    Config C;
+    const int rc = ensure_device(&D, &C);
+    if (rc)
+        return rc;
+    return hip_err(wc::launch_rx_demux(d_base, d_off, d_rec, n, d_tab, ns, d_sock, d_list, d_start,
+                                       d_scratch, (hipStream_t)stream));
+}
+
+int wc_rx_demux_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off,
+                     const uint16_t *h_frame_len, uint64_t n, const void *h_tab, uint32_t ns,
+                     uint8_t *h_verdict, struct wc_rx_record *h_rec, uint8_t *h_sock,
+                     uint32_t *h_list, uint64_t *h_start, uint64_t *h_drops)
+{
+    if (n > kRxSelectMax || ns > tab::kTabMaxSocks || (h_list != nullptr) != (h_start != nullptr))
+        return WC_EINVAL;
+    if (n == 0) {
+        if (h_start)
+            std::fill(h_start, h_start + kRxStarts, 0ull);
+        if (h_drops)
+            *h_drops = 0;
+        return WC_OK;
+    }
+    if (!h_verdict || !h_rec || !h_sock || !socktab_ok(h_tab, &ns))
+        return WC_EINVAL;
+    const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n,
+                              {{h_verdict, (uint8_t *)h_rec, h_sock}}, kKindRxDemux, h_tab, ns);
+    if (rc != WC_OK)
+        return rc;
+    if (h_drops) {
+        uint64_t drops = 0;
+        for (uint64_t i = 0; i < n; ++i)
+            drops += WC_RX_IS_DROP(h_verdict[i]);
+        *h_drops = drops;
+    }
+    if (!h_list)
+        return WC_OK;
+    // The per-socket runs by the calling thread: one counting pass over the n
+    // socket bytes, the starts, then every delivered index to its run's next
+    // place -- ascending i, so each run is in ring order.
+    uint64_t cnt[kRxStarts] = {}, next[kRxStarts];
+    for (uint64_t i = 0; i < n; ++i)
+        ++cnt[h_sock[i]];
+    cnt[WC_RX_SOCK_NONE] = 0; // (not delivered: in no run)
+    uint64_t at = 0;
+    for (uint64_t s = 0; s < ns; ++s) {
+        h_start[s] = next[s] = at;
+        at += cnt[s];
+    }
+    for (uint64_t s = ns; s < kRxStarts - 1; ++s)
+        h_start[s] = at;
+    next[WC_RX_SOCK_UNBOUND] = at;
+    h_start[kRxStarts - 1] = at + cnt[WC_RX_SOCK_UNBOUND];
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint8_t s = h_sock[i];
+        if (s < ns || s == WC_RX_SOCK_UNBOUND)
+            h_list[next[s]++] = (uint32_t)i;
+    }
     return WC_OK;
 }
 
