@@ -336,6 +336,115 @@ int wc_tx_seal_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off,
                     const uint16_t *h_frame_len, uint64_t n, uint32_t flags,
                     uint8_t *h_status, uint64_t *h_errors);
 
+/* --- TX build: Ethernet / IP / UDP headers written from a socket table ---- */
+
+/* The per-iov body of udp_tx (udp.c:189-220): mk_ip4_hdr / mk_ip6_hdr
+ * (ip4.c:153-189, ip6.c:127-161), the four UDP fields and mk_eth_hdr
+ * (eth.h:89-109), for a batch of frames whose payload is already in place.
+ * Everything is a function of a small per-socket tuple, a few per-iov values
+ * and the payload bytes; no header byte is written on the host.  Plain C types,
+ * little-endian layouts; "as stored" means network-order bytes, like the
+ * record ports. */
+#define WC_TX_BUILD_MAX_SOCKS 256
+#define WC_TX_SOCK_CONNECTED 1u   /* w_connected(s): raddr / rport / dmac are the socket's   */
+#define WC_TX_SOCK_ECN       2u   /* s->opt.enable_ecn                                        */
+
+struct wc_tx_sock {               /* 52 bytes: what udp_tx reads of one w_sock and its engine */
+    uint8_t  af;                  /* 4 or 6                                                   */
+    uint8_t  flags;               /* WC_TX_SOCK_*                                             */
+    uint16_t lport, rport;        /* as stored; rport ignored unless connected                */
+    uint8_t  smac[6], dmac[6];    /* v->w->mac; s->dmac (ignored unless connected)            */
+    uint8_t  pad[2];              /* ignored                                                  */
+    uint8_t  laddr[16], raddr[16];/* af 4: bytes 0..3 count. laddr: s->ws_laddr, or for an    */
+};                                /* unconnected socket the engine's interface address        */
+
+struct wc_tx_dst {                /* 24 bytes: an unconnected send's v->wv_addr / wv_port and  */
+    uint8_t  addr[16];            /* the MAC who_has() answered for it (eth.h:95-104)          */
+    uint8_t  dmac[6];
+    uint16_t port;                /* as stored */
+};
+
+struct wc_tx_desc {               /* 8 bytes per frame */
+    uint16_t data_len;            /* v->len: UDP payload bytes                                */
+    uint16_t ip_id;               /* ip->id as stored (the reference draws it at random and    */
+                                  /* does not swap it, ip4.c:167-168); ignored for af 6        */
+    uint8_t  sock;                /* index into the socket array                              */
+    uint8_t  tos;                 /* v->flags                                                 */
+    uint16_t dst;                 /* index into the destination array; ignored if connected   */
+};
+
+/* Pure host arithmetic (no GPU, no library state): WC_EINVAL for ns >
+ * WC_TX_BUILD_MAX_SOCKS, a NULL array with ns > 0, an af other than 4 / 6 or
+ * unknown flag bits; else WC_OK. */
+int wc_tx_socks_check(const struct wc_tx_sock *socks, uint32_t ns);
+
+/* Frame i starts at d_base + d_off[i] and may use slot_bytes bytes from there;
+ * its payload already lies at + 14 + hl + 8 (hl = 20 for af 4, 40 for af 6:
+ * where w_alloc_iov leaves v->buf).  The call writes the 14 + hl + 8 bytes in
+ * front of the payload -- all of them, whatever they held -- and nothing else,
+ * and sets d_frame_len[i] = 14 + hl + 8 + data_len (s->len, eth.c:124), 0 for
+ * every status but the two sealed ones.
+ *   Ethernet: dst = the socket's dmac if connected, else d_dsts[dst].dmac;
+ *     src = smac; type 08 00 / 86 dd.
+ *   IPv4 (ip4.c:153-189): 45, tos (| 2, ECT0, when (tos & 3) == 0 and the
+ *     socket has WC_TX_SOCK_ECN), total length 28 + data_len, ip_id as stored,
+ *     40 00 (DF), ttl ff, protocol 17, ip_cksum of these 20 bytes, src =
+ *     laddr[0..3], dst = raddr[0..3] if connected, else d_dsts[dst].addr[0..3].
+ *   IPv6 (ip6.c:127-161): the first word as the reference's ORs leave it on a
+ *     zeroed word -- with tos & 3 set, byte 0 = 0x60 | tos >> 4 and byte 1 =
+ *     (tos & 0x0f) << 4; without, byte 0 = 0x60 and byte 1 = 0 (the traffic
+ *     class is dropped, ip6.c:133), and byte 2 = 0x20 if the socket has
+ *     WC_TX_SOCK_ECN (ECN_ECT0 << 20 on the native word, ip6.c:138), else 0;
+ *     byte 3 = 0 -- then payload length 8 + data_len, next header 17, hop
+ *     limit ff, the 16-byte src and dst chosen as for IPv4.
+ *     One deliberate difference from the reference: mk_ip6_hdr ORs into bytes
+ *     1..3 of that word as the buffer left them; the build writes the whole
+ *     word.
+ *   UDP (udp.c:206-213): sport = lport, dport = rport if connected, else
+ *     d_dsts[dst].port, len 8 + data_len, cksum = payload_cksum(ip, hl + 8 +
+ *     data_len) with the field taken as 0, stored raw (a computed 0 stays 0,
+ *     as in the seal); with WC_TX_ZERO_UDP_CKSUM in `flags` the field is
+ *     written 0 and no payload byte is read (the per-socket option of
+ *     udp.c:212 is a per-call flag, as for the seal: the caller batches by it).
+ * d_status[i] is an enum wc_tx_status code; the checks run in this order and
+ * the first that fails names it:
+ *   1. sock >= ns, or the entry's af not 4 / 6:        WC_TX_MALFORMED
+ *   2. unconnected socket and dst >= ndst:              WC_TX_MALFORMED
+ *   3. 14 + hl + 8 + data_len > 65535:                  WC_TX_MALFORMED
+ *   4. the frame is longer than slot_bytes:             WC_TX_TRUNCATED
+ *   5. else WC_TX_SEALED, or WC_TX_SEALED_ZERO_UDP under the flag.
+ * An error frame is untouched.  For no status is a byte outside [frame, frame
+ * + frame_len) read or written, and no payload byte is ever written.
+ * d_out_ip_hdr / d_out_udp (optional) receive the two values, 0 where none is
+ * computed; *d_errors (device uint64, optional, accumulated) counts the
+ * WC_TX_IS_ERROR frames.  flags: WC_TX_ZERO_UDP_CKSUM | WC_TX_NO_STORE (the
+ * frames are only read, both out arrays required); any other bit is WC_EINVAL.
+ * n = 0 is WC_OK and looks at no pointer.  WC_EINVAL, before a device is
+ * touched: a NULL d_base / d_off / d_desc / d_frame_len / d_status, NULL
+ * d_socks with ns > 0 or d_dsts with ndst > 0, ns > 256, ndst > 65536, d_desc
+ * not 8-byte or d_socks / d_dsts not 4-byte aligned.  The frames of one call
+ * must not overlap (they may share 16-byte chunks and cache lines).  One
+ * asynchronous launch on `stream`; no library lock; the only atomic is the
+ * error count's, one per wave. */
+int wc_tx_build_ragged(void *d_base, const uint64_t *d_off, const struct wc_tx_desc *d_desc, uint64_t n,
+                       const struct wc_tx_sock *d_socks, uint32_t ns,
+                       const struct wc_tx_dst *d_dsts, uint32_t ndst, uint32_t slot_bytes, uint32_t flags,
+                       uint16_t *d_frame_len, uint8_t *d_status,
+                       uint16_t *d_out_ip_hdr, uint16_t *d_out_udp, uint64_t *d_errors, void *stream);
+
+/* Host-memory frames and tables: the calling thread runs the same checks and
+ * writes the headers of the frames that pass with both checksum fields 0 --
+ * every such frame must lie inside [h_base, h_base + h_bytes), else WC_EINVAL
+ * before any byte is written --, the device computes both values over the
+ * host paths of wc_tx_seal_host (never the resident server; it never writes
+ * host packet memory), and the calling thread stores them.  Synchronous;
+ * *h_errors (optional) = the WC_TX_IS_ERROR count.  WC_TX_NO_STORE is
+ * WC_EINVAL here. */
+int wc_tx_build_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off, const struct wc_tx_desc *h_desc,
+                     uint64_t n, const struct wc_tx_sock *h_socks, uint32_t ns,
+                     const struct wc_tx_dst *h_dsts, uint32_t ndst, uint32_t slot_bytes, uint32_t flags,
+                     uint16_t *h_frame_len, uint8_t *h_status, uint64_t *h_errors);
+
 /* --- host-memory batch (end-to-end: pinned H2D, kernel, D2H) ------------- */
 
 /* Same as wc_cksum_ragged, but every buffer is host memory: packet i is

@@ -23,7 +23,9 @@ from .cksum import (KIND_IP, KIND_PAYLOAD, SclkProbe, WcError, cksum_host, cksum
                     RX_DEMUX_MAX_SOCKS,
                     tx_seal_ragged, tx_seal_host, TX_NAMES, TX_ERRORS,
                     TX_SEALED, TX_SEALED_ZERO_UDP, TX_IP_ONLY, TX_NOT_UDP, TX_NOT_IP,
-                    TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED)
+                    TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED,
+                    tx_socks_check, tx_build_ragged, tx_build_host, TX_SOCK, TX_DST, TX_DESC,
+                    TX_SOCK_CONNECTED, TX_SOCK_ECN, TX_BUILD_MAX_SOCKS)
 
 __all__ = [
     "KIND_IP", "KIND_PAYLOAD", "SclkProbe", "WcError", "cksum_host", "cksum_host_multi",
@@ -43,4 +45,6 @@ __all__ = [
     "tx_seal_ragged", "tx_seal_host", "TX_NAMES", "TX_ERRORS", "TX_SEALED",
     "TX_SEALED_ZERO_UDP", "TX_IP_ONLY", "TX_NOT_UDP", "TX_NOT_IP", "TX_BAD_VERSION",
     "TX_MALFORMED", "TX_TRUNCATED",
+    "tx_socks_check", "tx_build_ragged", "tx_build_host", "TX_SOCK", "TX_DST", "TX_DESC",
+    "TX_SOCK_CONNECTED", "TX_SOCK_ECN", "TX_BUILD_MAX_SOCKS",
 ]

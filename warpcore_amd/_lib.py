@@ -48,6 +48,11 @@ SIGNATURES = {
                                 _vp]),
     "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "wc_tx_socks_check": (_int, [_vp, _u32]),
+    "wc_tx_build_ragged": (_int, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp,
+                                  _vp, _vp, _vp, _vp]),
+    "wc_tx_build_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _u32, _u32, _vp,
+                                _vp, _vp]),
     "wc_cksum_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _int]),
     "wc_cksum_ip_udp_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "wc_server_stats": (_int, [ctypes.POINTER(_u64), ctypes.POINTER(_u64),

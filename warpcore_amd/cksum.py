@@ -682,6 +682,125 @@ def tx_seal_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray,
 
 
 # --------------------------------------------------------------------------
+# TX build (the per-iov body of udp_tx: Ethernet / IP / UDP headers written
+# from a socket table, checksums included).
+
+# struct wc_tx_sock / wc_tx_dst / wc_tx_desc (include/warpcore_gpu/wc_cksum.h)
+TX_SOCK = np.dtype([("af", "u1"), ("flags", "u1"), ("lport", "<u2"), ("rport", "<u2"),
+                    ("smac", "u1", 6), ("dmac", "u1", 6), ("pad", "u1", 2),
+                    ("laddr", "u1", 16), ("raddr", "u1", 16)])
+TX_DST = np.dtype([("addr", "u1", 16), ("dmac", "u1", 6), ("port", "<u2")])
+TX_DESC = np.dtype([("data_len", "<u2"), ("ip_id", "<u2"), ("sock", "u1"), ("tos", "u1"),
+                    ("dst", "<u2")])
+assert (TX_SOCK.itemsize, TX_DST.itemsize, TX_DESC.itemsize) == (52, 24, 8)
+TX_SOCK_CONNECTED, TX_SOCK_ECN = 1, 2
+TX_BUILD_MAX_SOCKS = 256
+_TX_BUILD_MAX_DSTS = 65536
+
+
+def tx_socks_check(socks: np.ndarray) -> None:
+    """``ValueError`` for a socket array wc_tx_socks_check refuses: more than
+    256 entries, an af other than 4 / 6, unknown flag bits.  No GPU."""
+    socks = np.ascontiguousarray(socks, dtype=TX_SOCK).reshape(-1)
+    rc = _lib.active().wc_tx_socks_check(socks.ctypes.data if socks.size else None, socks.size)
+    if rc == -10001:
+        raise ValueError(f"TX socket array: at most {TX_BUILD_MAX_SOCKS} entries, af 4 or 6, "
+                         "flags of TX_SOCK_CONNECTED | TX_SOCK_ECN")
+    _check("wc_tx_socks_check", rc)
+
+
+def _table_tensor(name: str, t: torch.Tensor, dtype: np.dtype, most: int, device) -> int:
+    """Entries of a device table given as its contiguous bytes."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+        raise ValueError(f"{name} must be a device tensor on {device}")
+    if not t.is_contiguous() or _nbytes(t) % dtype.itemsize:
+        raise ValueError(f"{name} must be the contiguous bytes of {dtype.itemsize}-byte entries")
+    k = _nbytes(t) // dtype.itemsize
+    if k > most:
+        raise ValueError(f"{name}: at most {most} entries")
+    return k
+
+
+def tx_build_ragged(base: torch.Tensor, offsets: torch.Tensor, descs: torch.Tensor,
+                    socks: torch.Tensor, dsts: Optional[torch.Tensor], slot_bytes: int,
+                    zero_udp: bool = False, store: bool = True, stream=None,
+                    errors: Optional[torch.Tensor] = None):
+    """Write the Ethernet, IP and UDP headers of every frame in place
+    (wc_tx_build_ragged): frame ``i`` starts at ``base[off[i]]``, may use
+    ``slot_bytes`` bytes and already holds its payload behind the 42 (IPv4) or
+    62 (IPv6) header bytes.  ``descs`` / ``socks`` / ``dsts``: device tensors
+    holding the bytes of ``TX_DESC`` / ``TX_SOCK`` / ``TX_DST`` arrays
+    (``torch.from_numpy(a.view(np.uint8))``; ``dsts`` may be None).  Returns
+    (uint16 frame lengths -- 0 for an error frame --, uint8 status ``TX_*``,
+    uint16 IPv4 header checksums, uint16 UDP checksums, int64 count of
+    ``TX_ERRORS`` frames; a given ``errors`` tensor is accumulated into).  The
+    caller keeps every frame's slot inside ``base``."""
+    _same_device(base, offsets=offsets, descs=descs, socks=socks, dsts=dsts)
+    d = base.device
+    if not base.is_contiguous() or base.element_size() != 1:
+        raise ValueError("base must be a contiguous 1-byte tensor (the frames are written in place)")
+    n = offsets.numel()
+    if offsets.element_size() != 8 or offsets.is_floating_point() or not offsets.is_contiguous():
+        raise ValueError("offsets must be contiguous 8-byte integers")
+    if not descs.is_contiguous() or _nbytes(descs) != n * TX_DESC.itemsize:
+        raise ValueError("descs must be the contiguous bytes of one TX_DESC per frame")
+    ns = _table_tensor("socks", socks, TX_SOCK, TX_BUILD_MAX_SOCKS, d)
+    ndst = 0 if dsts is None else _table_tensor("dsts", dsts, TX_DST, _TX_BUILD_MAX_DSTS, d)
+    if not 0 <= int(slot_bytes) <= 0xFFFFFFFF:
+        raise ValueError("slot_bytes is a uint32")
+    frame_len = torch.empty(n, dtype=torch.uint16, device=d)
+    status = torch.empty(n, dtype=torch.uint8, device=d)
+    hdr = torch.empty(n, dtype=torch.uint16, device=d)
+    udp = torch.empty(n, dtype=torch.uint16, device=d)
+    if errors is None:
+        errors = torch.zeros(1, dtype=torch.int64, device=d)
+    elif (errors.numel() < 1 or errors.dtype not in (torch.int64, torch.uint64)
+          or not errors.is_contiguous() or errors.device != d):
+        raise ValueError("errors must be a contiguous int64 / uint64 device tensor (accumulated)")
+    flags = (_TX_ZERO_UDP_CKSUM if zero_udp else 0) | (0 if store else _TX_NO_STORE)
+    with _on_device(d):
+        _check("wc_tx_build_ragged", _lib.active().wc_tx_build_ragged(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(descs), n,
+            socks.data_ptr() if ns else None, ns, dsts.data_ptr() if ndst else None, ndst,
+            int(slot_bytes), flags, frame_len.data_ptr(), status.data_ptr(), hdr.data_ptr(),
+            udp.data_ptr(), errors.data_ptr(), _stream_ptr(stream, d)))
+    return frame_len, status, hdr, udp, errors
+
+
+def tx_build_host(buf: np.ndarray, offsets: np.ndarray, descs: np.ndarray, socks: np.ndarray,
+                  dsts: Optional[np.ndarray], slot_bytes: int,
+                  zero_udp: bool = False) -> Tuple[np.ndarray, np.ndarray, int]:
+    """tx_build_ragged over host memory (wc_tx_build_host, synchronous): the
+    headers are written into ``buf`` in place; (uint16 frame lengths, uint8
+    status codes, error count)."""
+    if not isinstance(buf, np.ndarray) or not buf.flags["C_CONTIGUOUS"] \
+            or not buf.flags["WRITEABLE"] or buf.dtype.itemsize != 1:
+        raise ValueError("tx_build_host writes the frames in place: buf must be a writable "
+                         "C-contiguous 1-byte numpy array")
+    flat = buf.reshape(-1).view(np.uint8)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    descs = np.ascontiguousarray(descs, dtype=TX_DESC).reshape(-1)
+    if descs.size != off.size:
+        raise ValueError("one TX_DESC per offset")
+    socks = np.ascontiguousarray(socks, dtype=TX_SOCK).reshape(-1)
+    dsts = np.zeros(0, TX_DST) if dsts is None else \
+        np.ascontiguousarray(dsts, dtype=TX_DST).reshape(-1)
+    if socks.size > TX_BUILD_MAX_SOCKS or dsts.size > _TX_BUILD_MAX_DSTS:
+        raise ValueError(f"at most {TX_BUILD_MAX_SOCKS} sockets and {_TX_BUILD_MAX_DSTS} "
+                         "destinations")
+    frame_len = np.empty(off.size, dtype=np.uint16)
+    status = np.empty(off.size, dtype=np.uint8)
+    errors = ctypes.c_uint64()
+    _check("wc_tx_build_host", _lib.active().wc_tx_build_host(
+        flat.ctypes.data, flat.size, off.ctypes.data, descs.ctypes.data, off.size,
+        socks.ctypes.data if socks.size else None, socks.size,
+        dsts.ctypes.data if dsts.size else None, dsts.size, int(slot_bytes),
+        _TX_ZERO_UDP_CKSUM if zero_udp else 0, frame_len.ctypes.data, status.ctypes.data,
+        ctypes.byref(errors)))
+    return frame_len, status, int(errors.value)
+
+
+# --------------------------------------------------------------------------
 # Host-memory batches (end-to-end path).
 
 def cksum_host(buf: np.ndarray, offsets: np.ndarray, lengths: np.ndarray,

@@ -216,6 +216,20 @@ hipError_t launch_tx_seal(void *base, const uint64_t *offs, const uint16_t *flen
                           uint32_t flags, uint8_t *status, uint16_t *out_ip, uint16_t *out_udp,
                           uint64_t *errors, bool nt, hipStream_t st);
 
+// TX build (wc_k_txbuild.hip): frame i starts at base + offs[i], its payload
+// already at + 14 + hl + 8; the headers in front of it are synthesised from
+// desc[i] (struct wc_tx_desc, 8-byte aligned), the socket table (ns struct
+// wc_tx_sock) and the destination table (ndst struct wc_tx_dst) and stored,
+// both checksums included.  frame_len[i] = the built frame's length (0 for an
+// error status), status[i] its enum wc_tx_status code; out_ip / out_udp
+// (optional) the two values; errors (optional) accumulates the error frames.
+// flags: kTxZeroUdp | kTxNoStore, as the seal's.
+hipError_t launch_tx_build(void *base, const uint64_t *offs, const void *desc, uint64_t n,
+                           const void *socks, uint32_t ns, const void *dsts, uint32_t ndst,
+                           uint32_t slot_bytes, uint32_t flags, uint16_t *frame_len,
+                           uint8_t *status, uint16_t *out_ip, uint16_t *out_udp, uint64_t *errors,
+                           bool nt, hipStream_t st);
+
 // Resident small-batch server (wc_k_serve.hip).  Host-mapped pinned memory:
 // one record per packet, written by the host (seq last), polled / read by the
 // server's waves; one result slot per packet, written by the GPU in one
