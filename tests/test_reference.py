@@ -244,6 +244,39 @@ def test_tx_model_values_are_the_references(ref, monkeypatch, name):
     np.testing.assert_array_equal(ours.buf, theirs.buf)
 
 
+def test_boundary_grid_checksum_decisions_are_the_references(ref):
+    """The same over tests/rx_edges.py's grid, the frames that stand on the
+    chain's thresholds: every frame whose verdict is one of the four a
+    checksum decides -- none left out -- gets it from the reference's
+    functions too (IHL < 5 and udp_len + hl < 20 included: len >= hl there)."""
+    import rx_edges
+    frames = rx_edges.grid()
+    verdict = rx_edges.oracle_verdicts(frames)
+    scope = np.flatnonzero(np.isin(verdict, RX_CKSUM_VERDICTS))
+    assert set(verdict[scope].tolist()) == set(RX_CKSUM_VERDICTS) and scope.size > 1000
+    for i in scope.tolist():
+        fr, flen, tag = frames[i]
+        assert ref_rx_verdict(ref, fr[:flen]) == int(verdict[i]), (
+            f"{tag}: oracle verdict {int(verdict[i])}")
+
+
+@pytest.mark.parametrize("zero_udp", [False, True])
+def test_boundary_grid_tx_model_values_are_the_references(ref, monkeypatch, zero_udp):
+    """tx_model's seal over the grid (fields garbled, as the GPU test hands it
+    over) with its two checksum calls answered by the reference: identical."""
+    import rx_edges
+    buf, offs, lens = rx_edges.packed(rx_edges.garbled(rx_edges.grid()), phase=3)
+    ours = tx_model.Expect(buf, offs, lens, zero_udp=zero_udp)
+    monkeypatch.setattr(tx_model, "c_oracle", ref)
+    theirs = tx_model.Expect(buf, offs, lens, zero_udp=zero_udp)
+    assert (ours.status == (tx_model.SEALED_ZERO_UDP if zero_udp else tx_model.SEALED)).sum() > 500
+    np.testing.assert_array_equal(ours.status, theirs.status)
+    np.testing.assert_array_equal(ours.ip_hdr, theirs.ip_hdr)
+    np.testing.assert_array_equal(ours.udp, theirs.udp)
+    assert [s.stores for s in ours.seals] == [s.stores for s in theirs.seals]
+    np.testing.assert_array_equal(ours.buf, theirs.buf)
+
+
 # ---------------------------------------------------------------------------
 # The guard and the fixture.
 
