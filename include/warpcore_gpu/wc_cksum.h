@@ -83,7 +83,12 @@ int wc_verify_ragged(const void *d_base, const uint64_t *d_off,
  * payload_cksum(pkt, len) and d_out_ip_hdr[i] = ip_cksum(pkt, ip4_hl(pkt[0]))
  * -- the IPv4 header checksum mk_ip4_hdr / ip4_rx compute (ip4.c:184-186,
  * 110-115) -- or 0 for an IPv6 packet, which has no header checksum
- * (ip6.c:83-113).  One read of the packet bytes for both. */
+ * (ip6.c:83-113).  One read of the packet bytes for both.  An IPv4 header
+ * (hl bytes, options included) must lie inside the caller's device buffer
+ * even where len is shorter: its checksum is defined whatever len is, and
+ * both calls read it whole.  len < hl itself is outside payload_cksum's
+ * defined inputs (the reference's len - hl wraps to ~4 GiB, in_cksum.c:164):
+ * d_out_payload[i] is then unspecified. */
 int wc_cksum_ip_udp_strided(const void *d_base, uint64_t stride, uint16_t len,
                             uint64_t n, uint16_t *d_out_ip_hdr,
                             uint16_t *d_out_payload, void *stream);
@@ -610,6 +615,13 @@ int wc_plan_strided(uint64_t base_addr, uint64_t stride, uint16_t len,
  * (segmented-prefix stream of a packed batch). */
 const char *wc_plan_strided_kernel(uint64_t base_addr, uint64_t stride, uint16_t len,
                                    uint64_t n, int kind);
+
+/* Both of the above for the fused call: the shape and the kernel family the
+ * dispatcher picks for wc_cksum_ip_udp_strided on that batch (payload_cksum
+ * with the header pass on, which takes neither the seg nor the lean route). */
+const char *wc_plan_strided_fused(uint64_t base_addr, uint64_t stride, uint16_t len,
+                                  uint64_t n, int *group, int *chunks_per_lane,
+                                  int *unroll, int *grid);
 
 const char *wc_strerror(int err);
 const char *wc_version(void);

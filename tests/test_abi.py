@@ -40,6 +40,31 @@ def test_python_binding_covers_header():
     assert declared_functions() == set(_lib.SIGNATURES)
 
 
+def test_fused_plan_introspection_entry():
+    """wc_plan_strided_fused stands beside wc_plan_strided_kernel: declared,
+    exported, bound with wc_plan_strided's four result pointers and the
+    family name for a result, and without a `kind` (the fused call has one);
+    the two older entries keep their signatures."""
+    import ctypes
+    assert "wc_plan_strided_fused" in declared_functions()
+    assert "wc_plan_strided_fused" in exported_symbols(_build.build_lib())
+    res, args = _lib.SIGNATURES["wc_plan_strided_fused"]
+    assert res is ctypes.c_char_p
+    plan_res, plan_args = _lib.SIGNATURES["wc_plan_strided"]
+    assert args == plan_args[:4] + plan_args[5:] and plan_res is ctypes.c_int
+    assert _lib.SIGNATURES["wc_plan_strided_kernel"] == (ctypes.c_char_p, plan_args[:5])
+    text = re.sub(r"\s+", " ", HEADER.read_text())
+    assert ("const char *wc_plan_strided_fused(uint64_t base_addr, uint64_t stride, uint16_t len, "
+            "uint64_t n, int *group, int *chunks_per_lane, int *unroll, int *grid);") in text
+    assert ("int wc_plan_strided(uint64_t base_addr, uint64_t stride, uint16_t len, uint64_t n, "
+            "int kind, int *group, int *chunks_per_lane, int *unroll, int *grid);") in text
+    import inspect
+    import warpcore_amd as wc
+    sig = inspect.signature(wc.plan_strided)
+    assert list(sig.parameters) == ["base_addr", "stride", "length", "n", "kind", "fused"]
+    assert sig.parameters["fused"].default is False and sig.parameters["kind"].default == "ip"
+
+
 def test_ctypes_load():
     lib = _lib.load()
     assert lib.wc_version().decode().startswith("wccksum")

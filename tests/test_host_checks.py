@@ -45,6 +45,43 @@ def test_ragged_bounds_checked():
                              wc.KIND_PAYLOAD)
 
 
+def test_fused_wrappers_need_the_whole_ipv4_header():
+    """The device-resident fused calls read an IPv4 header whole (hl bytes,
+    options included) even where len is shorter, as the host call does: the
+    wrappers refuse a batch whose header runs past the buffer, and accept it
+    where only len is short."""
+    base = torch.full((3 * 64 + 60,), 0x45, dtype=torch.uint8)
+    base[3 * 64] = 0x4F  # the last packet: IHL 15, its 60 header bytes end the buffer
+    cksum._check_strided(base[:-5], 0, 64, 24, 4, wc.KIND_PAYLOAD)  # len itself fits
+    cksum._check_strided_headers(base, 0, 64, 24, 4)
+    with pytest.raises(ValueError, match="IPv4 header"):
+        cksum._check_strided_headers(base[:-1], 0, 64, 24, 4)
+    cksum._check_strided_headers(base[:-5], 0, 64, 24, 3)    # without that packet
+    base[3 * 64] = 0x6F  # not IPv4: no header checksum, nothing read past len
+    cksum._check_strided_headers(base[:-5], 0, 64, 24, 4)
+    base[3 * 64] = 0x4F
+    phased = torch.full((7 + 3 * 64 + 60,), 0x4F, dtype=torch.uint8)
+    cksum._check_strided_headers(phased, 7, 64, 24, 4)
+    with pytest.raises(ValueError, match="IPv4 header"):   # at a phase, one byte short
+        cksum._check_strided_headers(phased[:-1], 7, 64, 24, 4)
+    with pytest.raises(ValueError, match="IPv4 header"):   # packed: several headers run past
+        cksum._check_strided_headers(phased[:7 + 10 * 24], 7, 24, 24, 10)
+    one = torch.full((59,), 0x4F, dtype=torch.uint8)
+    with pytest.raises(ValueError, match="IPv4 header"):   # stride 0: every packet is packet 0
+        cksum._check_strided_headers(one, 0, 0, 20, 1000)
+    # ragged
+    off = torch.tensor([0, 64, 192], dtype=torch.int64)
+    ln = torch.tensor([24, 30, 24], dtype=torch.int16)
+    cksum._ragged_bounds(base.numel(), off, ln, wc.KIND_PAYLOAD, base)
+    cksum._ragged_bounds(base.numel() - 1, off, ln, wc.KIND_PAYLOAD)  # the plain calls: len only
+    with pytest.raises(ValueError, match="IPv4 header"):
+        cksum._ragged_bounds(base.numel() - 1, off, ln, wc.KIND_PAYLOAD, base[:-1])
+    # the counter of verify_strided is a device int64, accumulated
+    with pytest.raises(ValueError, match="accumulated"):
+        cksum._bad_counter(torch.zeros(1, dtype=torch.int32), base.device)
+    assert cksum._bad_counter(None, base.device).item() == 0
+
+
 def test_length_range():
     for bad in (-1, 65536, 1 << 20):
         with pytest.raises(ValueError):

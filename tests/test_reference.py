@@ -278,6 +278,48 @@ def test_boundary_grid_tx_model_values_are_the_references(ref, monkeypatch, zero
 
 
 # ---------------------------------------------------------------------------
+# The strided grid (tests/strided_grid.py): what the GPU tests compare with.
+
+def test_strided_grid_expectations_are_the_references(ref):
+    """Every buffer of the strided grid at its largest n (the smaller n are
+    prefixes of it): the ip, payload and header-checksum expectations the GPU
+    tests use are what the reference's functions give on the same bytes; no
+    case left out (every payload case has len >= hl: asserted per buffer)."""
+    import strided_grid as sg
+    groups = sg.groups(sg.grid())
+    packets = 0
+    for case in groups:
+        buf, want = sg.buffer(case), sg.expect(case)
+        offs, lens = case.offs, np.full(case.n, case.length, np.uint16)
+        np.testing.assert_array_equal(ref.cksum_ragged(buf, offs, lens, kind=0), want["ip"],
+                                      err_msg=f"ip {case[:4]}")
+        if "payload" not in case.kinds:
+            continue
+        assert_payload_domain(buf, offs, lens, case.n)
+        np.testing.assert_array_equal(ref.cksum_ragged(buf, offs, lens, kind=1), want["payload"],
+                                      err_msg=f"payload {case[:4]}")
+        np.testing.assert_array_equal(refcases.hdr_expect(buf, offs), want["hdr"],
+                                      err_msg=f"hdr {case[:4]}")
+        packets += case.n
+    assert len(groups) == 2592 and packets > 300000
+
+
+def test_strided_grid_short_headers_are_the_references(ref):
+    """The IPv4 packets with 20 <= len < hl: the expected header checksums
+    are the reference's ip_cksum(pkt, hl).  (Its payload_cksum is never
+    called on them.)"""
+    import strided_grid as sg
+    cases = [c for c in sg.short_header_cases() if c.n == sg.N_SET[-1]]
+    assert len(cases) == 135
+    for case in cases:
+        np.testing.assert_array_equal(refcases.hdr_expect(sg.short_buffer(case), case.offs),
+                                      sg.short_expect(case), err_msg=str(case))
+    pk = sg.short_packets()
+    buf, offs, _ = pack(list(pk), align=1, lead=3)
+    np.testing.assert_array_equal(refcases.hdr_expect(buf, offs), sg.header_checksums(buf, offs))
+
+
+# ---------------------------------------------------------------------------
 # The guard and the fixture.
 
 def test_guard_refuses_len_below_header_length(monkeypatch):

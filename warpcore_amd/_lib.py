@@ -77,6 +77,9 @@ SIGNATURES = {
                                ctypes.POINTER(_int), ctypes.POINTER(_int),
                                ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "wc_plan_strided_kernel": (ctypes.c_char_p, [_u64, _u64, _u16, _u64, _int]),
+    "wc_plan_strided_fused": (ctypes.c_char_p, [_u64, _u64, _u16, _u64,
+                                                ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                                ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "wc_strerror": (ctypes.c_char_p, [_int]),
     "wc_version": (ctypes.c_char_p, []),
 }

@@ -117,8 +117,35 @@ def _check_strided(base: torch.Tensor, byte_offset: int, stride: int, length: in
                          f"runs past the {_nbytes(base)}-byte buffer")
 
 
+def _ip4_hl(first: torch.Tensor) -> torch.Tensor:
+    """4 * IHL of the packets whose first byte says IPv4, else 0 (int64)."""
+    b = first.to(torch.int64)
+    return torch.where(b >> 4 == 4, (b & 0x0F) * 4, torch.zeros_like(b))
+
+
+def _check_strided_headers(base: torch.Tensor, byte_offset: int, stride: int, length: int,
+                           n: int) -> None:
+    """The fused call reads every IPv4 header whole (hl bytes, options
+    included) even where len is shorter: it must lie inside base.  Only a
+    packet that starts in the buffer's last 60 bytes can fail that, so only
+    those first bytes are looked at (nothing is, from len 60 on)."""
+    if n == 0 or length >= 60:
+        return
+    nbytes = _nbytes(base)
+    room = nbytes - 60 - byte_offset  # a packet starting at or below it is safe
+    lo = 0 if room < 0 or stride == 0 else min(n, room // stride + 1)
+    hi = 1 if stride == 0 else n
+    if lo >= hi:
+        return
+    start = byte_offset + torch.arange(lo, hi, dtype=torch.int64, device=base.device) * stride
+    hl = _ip4_hl(base.view(torch.uint8).reshape(-1)[start])
+    if bool((start + hl > nbytes).any()):
+        raise ValueError("an IPv4 header (hl bytes, options included) runs past the buffer: it "
+                         "must lie inside it even where len is shorter")
+
+
 def _check_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor,
-                  kind: int, check: bool) -> int:
+                  kind: int, check: bool, fused: bool = False) -> int:
     _same_device(base, offsets=offsets, lengths=lengths)
     n = _check_ragged_shapes(offsets, lengths)
     if not base.is_contiguous():
@@ -126,7 +153,7 @@ def _check_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tens
     if check and n:
         # one device reduction + sync -- pass check=False on a hot loop whose
         # layout was validated once
-        _ragged_bounds(_nbytes(base), offsets, lengths, kind)
+        _ragged_bounds(_nbytes(base), offsets, lengths, kind, base if fused else None)
     return n
 
 
@@ -141,14 +168,21 @@ def _check_ragged_shapes(offsets: torch.Tensor, lengths: torch.Tensor) -> int:
 
 
 def _ragged_bounds(nbytes: int, offsets: torch.Tensor, lengths: torch.Tensor,
-                   kind: int) -> None:
-    """Every packet (and payload_cksum's 20 header bytes) inside [0, nbytes)."""
+                   kind: int, headers_of: Optional[torch.Tensor] = None) -> None:
+    """Every packet (and payload_cksum's 20 header bytes) inside [0, nbytes).
+    ``headers_of`` (the fused call: its base): every IPv4 header too, hl
+    bytes with the options, even where len is shorter."""
     off = offsets.view(torch.int64)
     ln = lengths.view(torch.int16).to(torch.int64) & 0xFFFF
     if kind == KIND_PAYLOAD:
         ln = torch.clamp(ln, min=20)
     if bool((off < 0).any()) or int((off + ln).max()) > nbytes:
         raise ValueError("a packet [off, off + len) runs past the buffer")
+    if headers_of is not None:
+        hl = _ip4_hl(headers_of.view(torch.uint8).reshape(-1)[off])
+        if int((off + hl).max()) > nbytes:
+            raise ValueError("an IPv4 header (hl bytes, options included) runs past the buffer: "
+                             "it must lie inside it even where len is shorter")
 
 
 class _on_device:
@@ -247,14 +281,25 @@ def cksum_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tenso
     return out
 
 
+def _bad_counter(bad: Optional[torch.Tensor], device) -> torch.Tensor:
+    if bad is None:
+        return torch.zeros(1, dtype=torch.int64, device=device)
+    if (bad.numel() < 1 or bad.dtype not in (torch.int64, torch.uint64)
+            or not bad.is_contiguous() or bad.device != device):
+        raise ValueError("bad must be a contiguous int64 / uint64 device tensor (accumulated)")
+    return bad
+
+
 def verify_strided(base, stride, length, n, kind="payload", out=None,
-                   stream=None, byte_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """RX check (udp.c:132-139): results plus the count of non-zero checksums."""
+                   stream=None, byte_offset: int = 0,
+                   bad: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """RX check (udp.c:132-139): results plus the count of non-zero checksums.
+    A given ``bad`` tensor is accumulated into, not reset."""
     k = _kind(kind)
     _same_device(base)
     _check_strided(base, byte_offset, stride, _check_len(length), n, k)
     out = _out_tensor(out, n, base.device)
-    bad = torch.zeros(1, dtype=torch.int64, device=base.device)
+    bad = _bad_counter(bad, base.device)
     with _on_device(base.device):
         _check("wc_verify_strided", _lib.active().wc_verify_strided(
             _dev_ptr(base) + byte_offset, stride, length, n, out.data_ptr(), bad.data_ptr(),
@@ -283,6 +328,7 @@ def cksum_ip_udp_strided(base: torch.Tensor, stride: int, length: int, n: int,
     for IPv6 packets."""
     _same_device(base)
     _check_strided(base, byte_offset, stride, _check_len(length), n, KIND_PAYLOAD)
+    _check_strided_headers(base, byte_offset, stride, length, n)
     hdr = _out_tensor(out_hdr, n, base.device)
     pay = _out_tensor(out, n, base.device)
     with _on_device(base.device):
@@ -295,7 +341,7 @@ def cksum_ip_udp_strided(base: torch.Tensor, stride: int, length: int, n: int,
 def cksum_ip_udp_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor,
                         stream=None, check: bool = True, out_hdr: Optional[torch.Tensor] = None,
                         out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    n = _check_ragged(base, offsets, lengths, KIND_PAYLOAD, check)
+    n = _check_ragged(base, offsets, lengths, KIND_PAYLOAD, check, fused=True)
     hdr = _out_tensor(out_hdr, n, base.device)
     pay = _out_tensor(out, n, base.device)
     with _on_device(base.device):
@@ -962,8 +1008,18 @@ class SclkProbe:
         return float((dc[ok] / dt[ok] * 100.0).median())
 
 
-def plan_strided(base_addr: int, stride: int, length: int, n: int, kind="ip") -> dict:
+def plan_strided(base_addr: int, stride: int, length: int, n: int, kind="ip",
+                 fused: bool = False) -> dict:
+    """The dispatcher's plan for a strided batch; ``fused``: the plan of
+    cksum_ip_udp_strided (``kind`` is then payload's, whatever is given)."""
     vals = [ctypes.c_int() for _ in range(4)]
+    names = ("group", "chunks_per_lane", "unroll", "grid")
+    if fused:
+        kernel = _lib.active().wc_plan_strided_fused(base_addr, stride, length, n,
+                                                     *[ctypes.byref(v) for v in vals])
+        plan = dict(zip(names, (v.value for v in vals)))
+        plan["kernel"] = kernel.decode()
+        return plan
     _check("wc_plan_strided", _lib.active().wc_plan_strided(
         base_addr, stride, length, n, _kind(kind), *[ctypes.byref(v) for v in vals]))
     plan = dict(zip(("group", "chunks_per_lane", "unroll", "grid"), (v.value for v in vals)))

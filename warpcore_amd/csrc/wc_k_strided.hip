@@ -252,8 +252,25 @@ k_cksum(const uint8_t *__restrict__ base, uint64_t stride, uint32_t len,
             }
             S = group_sum<G>(S);
             uint32_t Sh = 0;
-            if constexpr (HDR)
+            if constexpr (HDR) {
+                // An IPv4 header that runs past the chunks loaded for
+                // max(len, 20) bytes (options, len < hl): ip_cksum(ip, hl) is
+                // defined whatever len is (wc_cksum.h), so the round loads
+                // the header chunks behind the span, one per group lane (at
+                // most three: hl <= 60 and two chunks are always loaded).
+                // Wave-uniform; a round without such a packet only takes the
+                // ballot.
+                const uint32_t nhc =
+                    valid[u] && ph.v4 ? ((uint32_t)s[u] + ph.hl + 15u) >> 4 : 0u;
+                if (__ballot(nhc > nch[u])) {
+                    const uint32_t k = nch[u] + (uint32_t)gl;
+                    if (k < nhc) {
+                        const u32x4 t = load_chunk<NT>(c0[u] + 16ull * k);
+                        accum_arith<WC_KIND_IP>(t, 16 * (int)k - s[u], 0, (int)ph.hl, 0u, Eh, Oh);
+                    }
+                }
                 Sh = group_sum<G>(combine(Eh, Oh, s[u] & 1));
+            }
             const uint32_t rr = fold_not(S);
             if (lane_store) {
                 // Lane j of the wave takes packet p0 + j's result from its

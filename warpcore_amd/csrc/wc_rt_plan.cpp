@@ -531,4 +531,24 @@ const char *wc_plan_strided_kernel(uint64_t base_addr, uint64_t stride, uint16_t
     return p.lean ? "lean" : p.shape.group == 0 ? "seg" : "group";
 }
 
+const char *wc_plan_strided_fused(uint64_t base_addr, uint64_t stride, uint16_t len, uint64_t n,
+                                  int *group, int *chunks_per_lane, int *unroll, int *grid)
+{
+    Device *D = nullptr;
+    Config C;
+    if (ensure_device(&D, &C))
+        return "invalid";
+    // as batch_strided plans wc_cksum_ip_udp_strided: payload kind, header pass on
+    const Plan p = plan_strided(*D, C, base_addr, stride, len, n, WC_CKSUM_PAYLOAD, true);
+    if (group)
+        *group = p.shape.group;
+    if (chunks_per_lane)
+        *chunks_per_lane = p.shape.cpl;
+    if (unroll)
+        *unroll = p.shape.unroll;
+    if (grid)
+        *grid = p.grid;
+    return p.lean ? "lean" : p.shape.group == 0 ? "seg" : "group";
+}
+
 } // extern "C"
