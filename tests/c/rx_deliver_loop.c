@@ -26,12 +26,8 @@
 #include "warpcore_gpu/wc_cksum.h"
 #include "wc_oracle.h"
 
-#define BUF_SIZE 2048
-
-struct nm_slot {
-    uint32_t buf_idx;
-    uint16_t len;
-};
+#define RING_SEED 0x9E3779B97F4A7C15ull
+#include "ring.h"
 
 /* the w_iov fields udp_rx fills (warpcore.h), and the local address it looks
  * the socket up by */
@@ -44,21 +40,6 @@ struct iov {
     uint8_t addr[16];  /* wv_ip4 / wv_ip6 */
     uint8_t local[16]; /* local.addr */
 };
-
-static uint64_t rng = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(void)
-{
-    rng ^= rng << 13;
-    rng ^= rng >> 7;
-    rng ^= rng << 17;
-    return (uint32_t)(rng >> 11);
-}
-
-static void put16(uint8_t *p, uint16_t v)
-{
-    p[0] = (uint8_t)(v >> 8);
-    p[1] = (uint8_t)v;
-}
 
 enum { C_OK4, C_OK4_OPTS, C_OK6, C_NO_CKSUM, C_ULEN_SHORT, C_BAD_UDP, C_BAD_UDP_OPTS, C_BAD_IP,
        C_FRAGMENT, C_ICMP4, C_ICMP6, C_ARP, C_TRUNC, NCASES };
@@ -166,13 +147,7 @@ static void record_fill(const uint8_t *buf, const struct wc_rx_record *r, struct
     i->buf = buf + r->data_off;
 }
 
-#define FAIL(...)                                                              \
-    do {                                                                       \
-        printf("rx_deliver_loop: FAIL ");                                      \
-        printf(__VA_ARGS__);                                                   \
-        printf("\n");                                                          \
-        return 1;                                                              \
-    } while (0)
+#define FAIL(...) RING_FAIL("rx_deliver_loop", __VA_ARGS__)
 
 int main(int argc, char **argv)
 {
@@ -190,11 +165,7 @@ int main(int argc, char **argv)
         FAIL("alloc");
     for (uint32_t i = 0; i < nslots; i++)
         slot[i].buf_idx = i;
-    for (uint32_t i = nslots - 1; i > 0; i--) {
-        const uint32_t j = rnd() % (i + 1), t = slot[i].buf_idx;
-        slot[i].buf_idx = slot[j].buf_idx;
-        slot[j].buf_idx = t;
-    }
+    ring_shuffle(&slot[0].buf_idx, sizeof *slot, nslots);
     uint64_t delivered = 0, to_host = 0, dropped = 0;
     for (int pass = 0; pass < 2; pass++) {
         if (pass == 0 && wc_host_register(mem, mem_size) != WC_OK)

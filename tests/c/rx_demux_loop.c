@@ -28,28 +28,9 @@
 #include "warpcore_gpu/wc_cksum.h"
 #include "wc_oracle.h"
 
-#define BUF_SIZE 2048
+#define RING_SEED 0xD1B54A32D192ED03ull
+#include "ring.h"
 #define NSOCKS 12
-
-struct nm_slot {
-    uint32_t buf_idx;
-    uint16_t len;
-};
-
-static uint64_t rng = 0xD1B54A32D192ED03ull;
-static uint32_t rnd(void)
-{
-    rng ^= rng << 13;
-    rng ^= rng >> 7;
-    rng ^= rng << 17;
-    return (uint32_t)(rng >> 11);
-}
-
-static void put16(uint8_t *p, uint16_t v)
-{
-    p[0] = (uint8_t)(v >> 8);
-    p[1] = (uint8_t)v;
-}
 
 /* The engine's sockets: bound and connected ones sharing a local pair, an
  * IPv4 and an IPv6 socket alike in four address bytes and the port, one port
@@ -153,13 +134,7 @@ static int plain_lookup(const struct wc_rx_sock *socks, uint8_t af, const uint8_
     return WC_RX_SOCK_UNBOUND;
 }
 
-#define FAIL(...)                                                              \
-    do {                                                                       \
-        printf("rx_demux_loop: FAIL ");                                        \
-        printf(__VA_ARGS__);                                                   \
-        printf("\n");                                                          \
-        return 1;                                                              \
-    } while (0)
+#define FAIL(...) RING_FAIL("rx_demux_loop", __VA_ARGS__)
 
 int main(int argc, char **argv)
 {
@@ -184,11 +159,7 @@ int main(int argc, char **argv)
             FAIL("alloc");
     for (uint32_t i = 0; i < nslots; i++)
         slot[i].buf_idx = i;
-    for (uint32_t i = nslots - 1; i > 0; i--) {
-        const uint32_t j = rnd() % (i + 1), t = slot[i].buf_idx;
-        slot[i].buf_idx = slot[j].buf_idx;
-        slot[j].buf_idx = t;
-    }
+    ring_shuffle(&slot[0].buf_idx, sizeof *slot, nslots);
     make_socks(socks);
     uint64_t queued = 0, unbound = 0;
     for (int pass = 0; pass < 2; pass++) {

@@ -36,15 +36,10 @@
 #include "warpcore_gpu/wc_cksum.h"
 #include "wc_oracle.h"
 
-#define BUF_SIZE 2048
+#define RING_SEED 0x1234567887654321ull
+#include "ring.h"
 
-/* netmap_slot / netmap_ring, the fields w_nic_rx touches (netmap.h) */
-struct nm_slot {
-    uint32_t buf_idx;
-    uint16_t len;
-    uint16_t flags;
-    uint64_t ptr;
-};
+/* netmap_ring, the fields w_nic_rx touches (netmap.h) */
 struct nm_ring {
     uint32_t num_slots, nr_buf_size;
     uint32_t head, cur, tail;
@@ -54,21 +49,6 @@ struct nm_ring {
 static uint32_t nm_ring_next(const struct nm_ring *r, uint32_t i)
 {
     return i + 1 == r->num_slots ? 0 : i + 1;
-}
-
-static uint64_t rng = 0x1234567887654321ull;
-static uint32_t rnd(void)
-{
-    rng ^= rng << 13;
-    rng ^= rng >> 7;
-    rng ^= rng << 17;
-    return (uint32_t)(rng >> 11);
-}
-
-static void put16(uint8_t *p, uint16_t v)
-{
-    p[0] = (uint8_t)(v >> 8);
-    p[1] = (uint8_t)v;
 }
 
 enum {
@@ -176,13 +156,7 @@ static uint16_t make_frame(uint8_t *f, int k, int *want)
     return flen;
 }
 
-#define FAIL(...)                                                              \
-    do {                                                                       \
-        printf("rx_ring_loop: FAIL ");                                         \
-        printf(__VA_ARGS__);                                                   \
-        printf("\n");                                                          \
-        return 1;                                                              \
-    } while (0)
+#define FAIL(...) RING_FAIL("rx_ring_loop", __VA_ARGS__)
 
 int main(int argc, char **argv)
 {
@@ -203,11 +177,7 @@ int main(int argc, char **argv)
     /* buffers handed out in scrambled order (zero-copy swaps, netmap) */
     for (uint32_t i = 0; i < nbufs; i++)
         bufs[i] = i;
-    for (uint32_t i = nbufs - 1; i > 0; i--) {
-        const uint32_t j = rnd() % (i + 1), t = bufs[i];
-        bufs[i] = bufs[j];
-        bufs[j] = t;
-    }
+    ring_shuffle(bufs, sizeof *bufs, nbufs);
     if (oracle_only) {
         uint64_t seen[NCASES] = {0};
         for (uint32_t i = 0; i < 64u * NCASES * 8u; i++) {

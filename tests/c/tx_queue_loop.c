@@ -46,24 +46,10 @@
 #include "warpcore_gpu/wc_cksum.h"
 #include "wc_oracle.h"
 
-#define BUF_SIZE 2048
+#define RING_SEED 0x9E3779B97F4A7C15ull
+#include "ring.h"
 #define RING_SLOTS 64
 #define MAX_Q 5000
-
-static uint64_t rng = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(void)
-{
-    rng ^= rng << 13;
-    rng ^= rng >> 7;
-    rng ^= rng << 17;
-    return (uint32_t)(rng >> 11);
-}
-
-static void put16(uint8_t *p, uint16_t v) /* network order (bswap16 stores) */
-{
-    p[0] = (uint8_t)(v >> 8);
-    p[1] = (uint8_t)v;
-}
 
 enum { S_V4, S_V4_OPTS, S_V6, S_V4_ZERO, S_V6_ZERO, NSOCK };
 
@@ -130,13 +116,7 @@ static uint32_t build_headers(uint8_t *frame, const struct sock *s, struct iov *
     return hl;
 }
 
-#define FAIL(...)                                                              \
-    do {                                                                       \
-        printf("tx_queue_loop: FAIL ");                                        \
-        printf(__VA_ARGS__);                                                   \
-        printf("\n");                                                          \
-        return 1;                                                              \
-    } while (0)
+#define FAIL(...) RING_FAIL("tx_queue_loop", __VA_ARGS__)
 
 struct ring { /* a netmap TX ring: frames waiting for w_nic_tx */
     uint32_t idx[RING_SLOTS];
@@ -217,11 +197,7 @@ int main(int argc, char **argv)
                 const struct sock *s = &socks[k];
                 const uint32_t n = qlen[(qi + k + pass) % nq];
                 /* w_alloc: buffers in scrambled order */
-                for (uint32_t i = nbufs - 1; i > 0; i--) {
-                    const uint32_t j = rnd() % (i + 1), t = free_idx[i];
-                    free_idx[i] = free_idx[j];
-                    free_idx[j] = t;
-                }
+                ring_shuffle(free_idx, sizeof *free_idx, nbufs);
                 /* the application's payloads */
                 for (uint32_t i = 0; i < n; i++) {
                     q[i].idx = free_idx[i];

@@ -38,23 +38,9 @@
 #include "warpcore_gpu/wc_cksum.h"
 #include "wc_oracle.h"
 
-#define BUF_SIZE 2048
+#define RING_SEED 0x9E3779B97F4A7C15ull
+#include "ring.h"
 #define MAX_Q 5000
-
-static uint64_t rng = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(void)
-{
-    rng ^= rng << 13;
-    rng ^= rng >> 7;
-    rng ^= rng << 17;
-    return (uint32_t)(rng >> 11);
-}
-
-static void put16(uint8_t *p, uint16_t v) /* network order (bswap16 stores) */
-{
-    p[0] = (uint8_t)(v >> 8);
-    p[1] = (uint8_t)v;
-}
 
 enum { S_V4, S_V4_OPTS, S_V6, S_V4_ZERO, S_V6_ZERO, NSOCK };
 
@@ -140,13 +126,7 @@ static void oracle_finish(uint8_t *frame, const struct sock *s)
     }
 }
 
-#define FAIL(...)                                                              \
-    do {                                                                       \
-        printf("tx_seal_loop: FAIL ");                                         \
-        printf(__VA_ARGS__);                                                   \
-        printf("\n");                                                          \
-        return 1;                                                              \
-    } while (0)
+#define FAIL(...) RING_FAIL("tx_seal_loop", __VA_ARGS__)
 
 int main(void)
 {
@@ -206,11 +186,7 @@ int main(void)
                 const uint32_t n = qlen[qi];
                 const uint32_t hl = s->af6 ? 40 : 20 + (uint32_t)s->opt_hl;
                 /* w_alloc: buffers in scrambled order */
-                for (uint32_t i = nbufs - 1; i > 0; i--) {
-                    const uint32_t j = rnd() % (i + 1), t = free_idx[i];
-                    free_idx[i] = free_idx[j];
-                    free_idx[j] = t;
-                }
+                ring_shuffle(free_idx, sizeof *free_idx, nbufs);
                 /* the application's payloads, then udp_tx's headers: the
                  * queue as (buffer offset, frame length) */
                 for (uint32_t i = 0; i < n; i++) {

@@ -265,6 +265,37 @@ def test_select_dense_and_sparse_extremes(gpu):
     assert int(cnt.item()) == 1 and got[0] == n - 2 and (got[1:] == SENTINEL).all()
 
 
+# A select block is 256 chunks of 16 verdict bytes = 4096 verdicts (kSelBlock)
+# and the one-workgroup scan takes 1024 block counts per iteration (kSelScan):
+# 1024 * 4096 = 2^22 verdicts per iteration, so 2^22 + 17 is the smallest
+# shape with a second one (1025 blocks at offset 0, 1026 chunks' worth at
+# offset 5), and 2^26 + 17 runs seventeen, the carry growing past 2^26.
+SELECT_CARRY_N = [1024 * 4096 + 17, 1024 * 4096 * 16 + 17]
+
+
+@pytest.mark.parametrize("shift", [0, 5])
+@pytest.mark.parametrize("n", SELECT_CARRY_N)
+def test_select_carry_across_scan_iterations(gpu, n, shift):
+    """Every verdict matching -- each scan iteration adds a full 2^22 to the
+    carry, and the last block's offset is the whole carry -- and exactly one
+    match, in the last byte, whose offset is 0 after any number of iterations;
+    at a 16-byte boundary and 5 bytes past one.  Expectations are arange(n)
+    and [n - 1]; compared on the device."""
+    t = torch.full((n + shift + 16,), wc.RX_OK_NO_CKSUM, dtype=torch.uint8, device=gpu)
+    tv = t[shift:shift + n]  # (the bytes around it would match)
+    assert tv.data_ptr() % 16 == shift
+    lst = torch.full((n,), SENTINEL - (1 << 32), dtype=torch.int32, device=gpu)
+    tv.fill_(wc.RX_NOT_IP)
+    tv[n - 1] = wc.RX_OK
+    got, cnt = wc.rx_select(tv, wc.RX_MASK_DELIVER, out=lst)
+    assert int(cnt.item()) == 1 and int(got[0].item()) == n - 1
+    assert bool((got[1:] == SENTINEL - (1 << 32)).all())
+    tv.fill_(wc.RX_OK_NO_CKSUM)
+    got, cnt = wc.rx_select(tv, wc.RX_MASK_DELIVER, out=lst)
+    assert int(cnt.item()) == n
+    assert bool((got == torch.arange(n, dtype=torch.int32, device=gpu)).all())
+
+
 def test_deliver_many_frames_repeated(gpu, mixed):
     """More frames than one scan iteration's blocks cover would need real
     frames by the million; the calls only read, so 2^18 + 1 offsets point at

@@ -188,6 +188,46 @@ def test_demux_254_sockets_many_blocks(gpu):
     run_demux(buf, offs[idx], lens[idx], w, w.exp.take(idx), gpu)
 
 
+@pytest.fixture(scope="module")
+def small_v4():
+    """254 bound IPv4 sockets and, in 64-byte slots, minimal frames (42 header
+    bytes, up to 6 of payload) for all of them but 100..109, then strays."""
+    rng = np.random.default_rng(12)
+    socks = np.array([model.sock(4, A4[5], be16(6000 + i), rng=rng) for i in range(254)],
+                     dtype=model.SOCK)
+    to = [i for i in range(254) if not 100 <= i < 110]
+    frames = [frame_to(rng, socks[i], max_payload=6) for i in to * 3] + \
+        [udp_frame(rng, 4, A4[6], be16(7000 + k), PEER4, be16(9), max_payload=6) for k in range(40)]
+    assert max(flen for _, flen in frames) <= 64
+    return socks, frames
+
+
+@pytest.mark.parametrize("ns", [254, 0])
+def test_demux_scan_second_iteration(gpu, small_v4, ns):
+    """n = 17 blocks + 1 frame -> 18 blocks; with 254 sockets (ns + 1) * 18 =
+    4590 counts, just past the 1024 threads x 4 counts of one scan iteration,
+    so the second one starts inside a class's row with the carry of the first.
+    Sockets 0 and 253 and the unbound class have frames, sockets 100..109 have
+    none (consecutive equal starts); the frames are drawn at random, so every
+    block's counts differ.  With no socket the scan's row 0 is the unbound
+    row and every delivered frame is in it."""
+    socks, frames = small_v4
+    w = World(socks[:ns], frames)
+    n = 17 * BLOCK + 1
+    assert (ns + 1) * (n // BLOCK + 1) == (4590 if ns else 18) and 4590 > 1024 * 4
+    rng = np.random.default_rng(13)
+    buf, offs, lens = slot_ring(w.frames, slot=64, rng=rng)
+    idx = rng.integers(0, len(frames), n)
+    exp = w.exp.take(idx)
+    if ns:
+        st = exp.start.astype(np.int64)
+        assert st[1] > st[0] == 0 and st[254] > st[253] and st[255] > st[254]
+        assert (st[100:111] == st[100]).all() and st[111] > st[110]
+    else:
+        assert (exp.start[:255] == 0).all() and exp.start[255] == n
+    run_demux(buf, offs[idx], lens[idx], w, exp, gpu)
+
+
 def test_demux_all_unbound(gpu, world):
     rng = np.random.default_rng(6)
     w = World(world.socks, [stray_frame(rng) for _ in range(700)])

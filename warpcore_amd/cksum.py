@@ -32,6 +32,9 @@ _KINDS = {"ip": KIND_IP, "payload": KIND_PAYLOAD, KIND_IP: KIND_IP,
           KIND_PAYLOAD: KIND_PAYLOAD}
 
 
+_WC_EINVAL = -10001  # WC_EINVAL (include/warpcore_gpu/wc_cksum.h)
+
+
 class WcError(RuntimeError):
     """A libwccksum call returned an error code."""
 
@@ -145,11 +148,16 @@ def _check_strided_headers(base: torch.Tensor, byte_offset: int, stride: int, le
 
 
 def _check_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor,
-                  kind: int, check: bool, fused: bool = False) -> int:
+                  kind: int, check: bool, fused: bool = False, in_place: bool = False) -> int:
+    """The argument rules of every packet / frame batch call; returns n.
+    ``fused``: the IPv4 headers are checked too; ``in_place``: the call writes
+    into ``base``."""
     _same_device(base, offsets=offsets, lengths=lengths)
     n = _check_ragged_shapes(offsets, lengths)
     if not base.is_contiguous():
         raise ValueError("base must be contiguous")
+    if in_place and base.element_size() != 1:
+        raise ValueError("base must be a 1-byte tensor (the frames are written in place)")
     if check and n:
         # one device reduction + sync -- pass check=False on a hot loop whose
         # layout was validated once
@@ -281,13 +289,15 @@ def cksum_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tenso
     return out
 
 
-def _bad_counter(bad: Optional[torch.Tensor], device) -> torch.Tensor:
-    if bad is None:
+def _bad_counter(t: Optional[torch.Tensor], device, name: str = "bad") -> torch.Tensor:
+    """The counter argument ``name`` of a call that accumulates into it, or a
+    zeroed one of this module's."""
+    if t is None:
         return torch.zeros(1, dtype=torch.int64, device=device)
-    if (bad.numel() < 1 or bad.dtype not in (torch.int64, torch.uint64)
-            or not bad.is_contiguous() or bad.device != device):
-        raise ValueError("bad must be a contiguous int64 / uint64 device tensor (accumulated)")
-    return bad
+    if (t.numel() < 1 or t.dtype not in (torch.int64, torch.uint64)
+            or not t.is_contiguous() or t.device != device):
+        raise ValueError(f"{name} must be a contiguous int64 / uint64 device tensor (accumulated)")
+    return t
 
 
 def verify_strided(base, stride, length, n, kind="payload", out=None,
@@ -372,22 +382,13 @@ def rx_verdict_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: tor
     (``RX_*``) and the number of frames the reference's RX path drops.  No
     header is parsed on the host (wc_rx_verdict_ragged).  A given ``drops``
     tensor is accumulated into, not reset."""
-    _same_device(base, offsets=offsets, lengths=frame_lens)
-    n = _check_ragged_shapes(offsets, frame_lens)
-    if not base.is_contiguous():
-        raise ValueError("base must be contiguous")
-    if check and n:
-        _ragged_bounds(_nbytes(base), offsets, frame_lens, KIND_IP)
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
     if out is None:
         out = torch.empty(n, dtype=torch.uint8, device=base.device)
     if out.numel() < n or out.element_size() != 1 or not out.is_contiguous() \
             or out.device != base.device:
         raise ValueError(f"out must be a contiguous 1-byte tensor of >= n entries on {base.device}")
-    if drops is None:
-        drops = torch.zeros(1, dtype=torch.int64, device=base.device)
-    elif (drops.numel() < 1 or drops.dtype not in (torch.int64, torch.uint64)
-          or not drops.is_contiguous() or drops.device != base.device):
-        raise ValueError("drops must be a contiguous int64 / uint64 device tensor (accumulated)")
+    drops = _bad_counter(drops, base.device, "drops")
     with _on_device(base.device):
         _check("wc_rx_verdict_ragged", _lib.active().wc_rx_verdict_ragged(
             _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, out.data_ptr(),
@@ -399,14 +400,7 @@ def rx_verdict_host(buf: np.ndarray, offsets: np.ndarray,
                     frame_lens: np.ndarray) -> Tuple[np.ndarray, int]:
     """rx_verdict_ragged over host memory (wc_rx_verdict_host, synchronous):
     (uint8 verdicts, drop count)."""
-    buf = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
-    lens_in = np.asarray(frame_lens)
-    if lens_in.size and (lens_in.min() < 0 or lens_in.max() > 0xFFFF):
-        raise ValueError("frame lengths are uint16 (netmap_slot.len)")
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
-    lens = np.ascontiguousarray(lens_in, dtype=np.uint16)
-    if off.shape != lens.shape:
-        raise ValueError("offsets and frame_lens must have the same shape")
+    buf, off, lens = _host_batch_args(buf, offsets, frame_lens)
     out = np.empty(off.size, dtype=np.uint8)
     drops = ctypes.c_uint64()
     _check("wc_rx_verdict_host", _lib.active().wc_rx_verdict_host(
@@ -433,9 +427,23 @@ def rx_select_scratch(n: int) -> int:
     return int(_lib.active().wc_rx_select_scratch(int(n)))
 
 
-def _select_scratch(n: int, device) -> torch.Tensor:
+def _scratch(nbytes: int, device) -> torch.Tensor:
     # int32 elements: a torch allocation is aligned far beyond the 4 bytes asked
-    return torch.empty(max(1, (rx_select_scratch(n) + 3) // 4), dtype=torch.int32, device=device)
+    return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.int32, device=device)
+
+
+def _index_list(out_list: Optional[torch.Tensor], n: int, device) -> Tuple[torch.Tensor, bool]:
+    """The uint32 list handed to the library -- ``out_list`` or one of this
+    module's -- and whether it is this module's.  It is never empty (an empty
+    tensor, a zero-length slice included, has a NULL data pointer, which would
+    read as "no list"); an own one is cut to n entries where it is returned."""
+    own = out_list is None
+    lst = torch.empty(max(n, 1), dtype=torch.uint32, device=device) if own else out_list
+    if lst.numel() < max(n, 1) or lst.element_size() != 4 or not lst.is_contiguous() \
+            or lst.device != device:
+        raise ValueError(f"out_list must be a contiguous 4-byte tensor of >= max(n, 1) "
+                         f"entries on {device}")
+    return lst, own
 
 
 def rx_select(verdicts: torch.Tensor, mask: int, out: Optional[torch.Tensor] = None,
@@ -460,7 +468,7 @@ def rx_select(verdicts: torch.Tensor, mask: int, out: Optional[torch.Tensor] = N
         raise ValueError(f"out must be a contiguous 4-byte tensor of >= n entries on "
                          f"{verdicts.device}")
     count = torch.zeros(1, dtype=torch.int64, device=verdicts.device)
-    scratch = _select_scratch(n, verdicts.device)
+    scratch = _scratch(rx_select_scratch(n), verdicts.device)
     with _on_device(verdicts.device):
         _check("wc_rx_select", _lib.active().wc_rx_select(
             verdicts.data_ptr(), n, int(mask), out.data_ptr(), count.data_ptr(),
@@ -478,32 +486,18 @@ def rx_deliver_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: tor
     verdict is RX_OK / RX_OK_NO_CKSUM; ``list`` / ``count`` as rx_select gives
     them for ``RX_MASK_DELIVER`` (None, None with ``want_list=False``);
     ``drops`` as rx_verdict_ragged.  No header is parsed on the host."""
-    _same_device(base, offsets=offsets, lengths=frame_lens)
-    n = _check_ragged_shapes(offsets, frame_lens)
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
     if n > _RX_SELECT_MAX:
         raise ValueError("at most 2^32 frames (the indices are uint32)")
-    if not base.is_contiguous():
-        raise ValueError("base must be contiguous")
-    if check and n:
-        _ragged_bounds(_nbytes(base), offsets, frame_lens, KIND_IP)
     d = base.device
     verdicts = torch.empty(n, dtype=torch.uint8, device=d)
     records = torch.empty((n, RX_RECORD.itemsize), dtype=torch.uint8, device=d)
     drops = torch.zeros(1, dtype=torch.int64, device=d)
     lst = cnt = scratch = None
     if want_list:
-        # The pointer handed to the library comes from a tensor that is never
-        # empty (an empty one, a zero-length slice included, has a NULL data
-        # pointer, which would read as "no list"); only what is returned is
-        # cut to n entries.
-        own = out_list is None
-        lst = torch.empty(max(n, 1), dtype=torch.uint32, device=d) if own else out_list
-        if lst.numel() < max(n, 1) or lst.element_size() != 4 or not lst.is_contiguous() \
-                or lst.device != d:
-            raise ValueError(f"out_list must be a contiguous 4-byte tensor of >= max(n, 1) "
-                             f"entries on {d}")
+        lst, own = _index_list(out_list, n, d)
         cnt = torch.zeros(1, dtype=torch.int64, device=d)
-        scratch = _select_scratch(n, d)
+        scratch = _scratch(rx_select_scratch(n), d)
     with _on_device(d):
         _check("wc_rx_deliver_ragged", _lib.active().wc_rx_deliver_ragged(
             _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, verdicts.data_ptr(),
@@ -560,7 +554,7 @@ def rx_socktab_build(socks: np.ndarray) -> np.ndarray:
         raise ValueError(f"at most {RX_DEMUX_MAX_SOCKS} sockets (the ids are uint8)")
     tab = np.zeros(rx_socktab_bytes(ns) // 4, dtype=np.uint32)
     rc = _lib.active().wc_rx_socktab_build(socks.ctypes.data if ns else None, ns, tab.ctypes.data)
-    if rc == -10001:
+    if rc == _WC_EINVAL:
         raise ValueError("socket table: af must be 4 or 6, connected 0 or 1, every tuple distinct")
     _check("wc_rx_socktab_build", rc)
     return tab.view(np.uint8)
@@ -617,16 +611,10 @@ def rx_demux(base: torch.Tensor, offsets: torch.Tensor, records: torch.Tensor,
     sock = torch.empty(n, dtype=torch.uint8, device=d)
     lst = start = None
     if want_list:
-        own = out_list is None
-        lst = torch.empty(max(n, 1), dtype=torch.uint32, device=d) if own else out_list
-        if lst.numel() < max(n, 1) or lst.element_size() != 4 or not lst.is_contiguous() \
-                or lst.device != d:
-            raise ValueError(f"out_list must be a contiguous 4-byte tensor of >= max(n, 1) "
-                             f"entries on {d}")
+        lst, own = _index_list(out_list, n, d)
         start = torch.zeros(_RX_STARTS, dtype=torch.int64, device=d)
         if scratch is None:
-            scratch = torch.empty(max(1, (rx_demux_scratch(n) + 3) // 4), dtype=torch.int32,
-                                  device=d)
+            scratch = _scratch(rx_demux_scratch(n), d)
         elif _nbytes(scratch) < rx_demux_scratch(n) or scratch.device != d:
             raise ValueError(f"scratch must hold rx_demux_scratch(n) bytes on {d}")
     with _on_device(d):
@@ -688,14 +676,7 @@ def tx_seal_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.
     (uint8 status ``TX_*`` per frame, uint16 header checksums, uint16 UDP
     checksums -- 0 where none is computed --, int64 count of ``TX_ERRORS``
     frames)."""
-    _same_device(base, offsets=offsets, lengths=frame_lens)
-    n = _check_ragged_shapes(offsets, frame_lens)
-    if not base.is_contiguous():
-        raise ValueError("base must be contiguous")
-    if base.element_size() != 1:
-        raise ValueError("base must be a 1-byte tensor (the frames are written in place)")
-    if check and n:
-        _ragged_bounds(_nbytes(base), offsets, frame_lens, KIND_IP)
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, in_place=True)
     status = torch.empty(n, dtype=torch.uint8, device=base.device)
     hdr = torch.empty(n, dtype=torch.uint16, device=base.device)
     udp = torch.empty(n, dtype=torch.uint16, device=base.device)
@@ -709,15 +690,20 @@ def tx_seal_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.
     return status, hdr, udp, errors
 
 
+def _in_place_bytes(func: str, buf: np.ndarray) -> np.ndarray:
+    """``buf``'s own bytes, flat, for a host call that writes the frames."""
+    if not isinstance(buf, np.ndarray) or not buf.flags["C_CONTIGUOUS"] \
+            or not buf.flags["WRITEABLE"] or buf.dtype.itemsize != 1:
+        raise ValueError(f"{func} writes the frames in place: buf must be a writable "
+                         "C-contiguous 1-byte numpy array")
+    return buf.reshape(-1).view(np.uint8)
+
+
 def tx_seal_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray,
                  zero_udp: bool = False) -> Tuple[np.ndarray, int]:
     """tx_seal_ragged over host memory (wc_tx_seal_host, synchronous): the
     frames in ``buf`` are sealed in place; (uint8 status codes, error count)."""
-    if not isinstance(buf, np.ndarray) or not buf.flags["C_CONTIGUOUS"] \
-            or not buf.flags["WRITEABLE"] or buf.dtype.itemsize != 1:
-        raise ValueError("tx_seal_host writes the frames in place: buf must be a writable "
-                         "C-contiguous 1-byte numpy array")
-    flat = buf.reshape(-1).view(np.uint8)
+    flat = _in_place_bytes("tx_seal_host", buf)
     _, off, lens = _host_batch_args(flat, offsets, frame_lens)
     status = np.empty(off.size, dtype=np.uint8)
     errors = ctypes.c_uint64()
@@ -749,7 +735,7 @@ def tx_socks_check(socks: np.ndarray) -> None:
     256 entries, an af other than 4 / 6, unknown flag bits.  No GPU."""
     socks = np.ascontiguousarray(socks, dtype=TX_SOCK).reshape(-1)
     rc = _lib.active().wc_tx_socks_check(socks.ctypes.data if socks.size else None, socks.size)
-    if rc == -10001:
+    if rc == _WC_EINVAL:
         raise ValueError(f"TX socket array: at most {TX_BUILD_MAX_SOCKS} entries, af 4 or 6, "
                          "flags of TX_SOCK_CONNECTED | TX_SOCK_ECN")
     _check("wc_tx_socks_check", rc)
@@ -798,11 +784,7 @@ def tx_build_ragged(base: torch.Tensor, offsets: torch.Tensor, descs: torch.Tens
     status = torch.empty(n, dtype=torch.uint8, device=d)
     hdr = torch.empty(n, dtype=torch.uint16, device=d)
     udp = torch.empty(n, dtype=torch.uint16, device=d)
-    if errors is None:
-        errors = torch.zeros(1, dtype=torch.int64, device=d)
-    elif (errors.numel() < 1 or errors.dtype not in (torch.int64, torch.uint64)
-          or not errors.is_contiguous() or errors.device != d):
-        raise ValueError("errors must be a contiguous int64 / uint64 device tensor (accumulated)")
+    errors = _bad_counter(errors, d, "errors")
     flags = (_TX_ZERO_UDP_CKSUM if zero_udp else 0) | (0 if store else _TX_NO_STORE)
     with _on_device(d):
         _check("wc_tx_build_ragged", _lib.active().wc_tx_build_ragged(
@@ -819,11 +801,7 @@ def tx_build_host(buf: np.ndarray, offsets: np.ndarray, descs: np.ndarray, socks
     """tx_build_ragged over host memory (wc_tx_build_host, synchronous): the
     headers are written into ``buf`` in place; (uint16 frame lengths, uint8
     status codes, error count)."""
-    if not isinstance(buf, np.ndarray) or not buf.flags["C_CONTIGUOUS"] \
-            or not buf.flags["WRITEABLE"] or buf.dtype.itemsize != 1:
-        raise ValueError("tx_build_host writes the frames in place: buf must be a writable "
-                         "C-contiguous 1-byte numpy array")
-    flat = buf.reshape(-1).view(np.uint8)
+    flat = _in_place_bytes("tx_build_host", buf)
     off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
     descs = np.ascontiguousarray(descs, dtype=TX_DESC).reshape(-1)
     if descs.size != off.size:
@@ -855,17 +833,7 @@ def cksum_host(buf: np.ndarray, offsets: np.ndarray, lengths: np.ndarray,
 
     Small batches in a registered buffer are read in place by one kernel;
     larger ones are streamed over pinned H2D copies (wc_cksum_host)."""
-    buf = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
-    lens_in = np.asarray(lengths)
-    if lens_in.size and (lens_in.min() < 0 or lens_in.max() > 0xFFFF):
-        raise ValueError("len is a uint16 in the reference (0..65535)")
-    offs_in = np.asarray(offsets)
-    if offs_in.size and offs_in.dtype.kind == "i" and offs_in.min() < 0:
-        raise ValueError("negative offset")
-    if offs_in.shape != lens_in.shape:
-        raise ValueError("offsets and lengths must have the same shape")
-    off = np.ascontiguousarray(offs_in, dtype=np.uint64)
-    lens = np.ascontiguousarray(lens_in, dtype=np.uint16)
+    buf, off, lens = _host_batch_args(buf, offsets, lengths)
     out = np.empty(off.size, dtype=np.uint16)
     _check("wc_cksum_host", _lib.active().wc_cksum_host(
         buf.ctypes.data, buf.size, off.ctypes.data, lens.ctypes.data, off.size,
@@ -1013,18 +981,15 @@ def plan_strided(base_addr: int, stride: int, length: int, n: int, kind="ip",
     """The dispatcher's plan for a strided batch; ``fused``: the plan of
     cksum_ip_udp_strided (``kind`` is then payload's, whatever is given)."""
     vals = [ctypes.c_int() for _ in range(4)]
-    names = ("group", "chunks_per_lane", "unroll", "grid")
+    refs = [ctypes.byref(v) for v in vals]
     if fused:
-        kernel = _lib.active().wc_plan_strided_fused(base_addr, stride, length, n,
-                                                     *[ctypes.byref(v) for v in vals])
-        plan = dict(zip(names, (v.value for v in vals)))
-        plan["kernel"] = kernel.decode()
-        return plan
-    _check("wc_plan_strided", _lib.active().wc_plan_strided(
-        base_addr, stride, length, n, _kind(kind), *[ctypes.byref(v) for v in vals]))
+        kernel = _lib.active().wc_plan_strided_fused(base_addr, stride, length, n, *refs)
+    else:
+        _check("wc_plan_strided", _lib.active().wc_plan_strided(
+            base_addr, stride, length, n, _kind(kind), *refs))
+        kernel = _lib.active().wc_plan_strided_kernel(base_addr, stride, length, n, _kind(kind))
     plan = dict(zip(("group", "chunks_per_lane", "unroll", "grid"), (v.value for v in vals)))
-    plan["kernel"] = _lib.active().wc_plan_strided_kernel(base_addr, stride, length, n,
-                                                        _kind(kind)).decode()
+    plan["kernel"] = kernel.decode()
     return plan
 
 
@@ -1075,14 +1040,7 @@ def shard_devices() -> list:
 def cksum_host_multi(buf: np.ndarray, offsets: np.ndarray, lengths: np.ndarray,
                      kind="ip") -> np.ndarray:
     """cksum_host split evenly over the shard devices (wc_cksum_host_multi)."""
-    buf = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
-    lens_in = np.asarray(lengths)
-    if lens_in.size and (lens_in.min() < 0 or lens_in.max() > 0xFFFF):
-        raise ValueError("len is a uint16 in the reference (0..65535)")
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
-    lens = np.ascontiguousarray(lens_in, dtype=np.uint16)
-    if off.shape != lens.shape:
-        raise ValueError("offsets and lengths must have the same shape")
+    buf, off, lens = _host_batch_args(buf, offsets, lengths)
     out = np.empty(off.size, dtype=np.uint16)
     _check("wc_cksum_host_multi", _lib.active().wc_cksum_host_multi(
         buf.ctypes.data, buf.size, off.ctypes.data, lens.ctypes.data, off.size,

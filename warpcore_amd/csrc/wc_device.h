@@ -473,6 +473,63 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v)
     return v;
 }
 
+// Block-wide exclusive prefix of v (every thread of the THREADS-thread block
+// calls it): the DPP wave prefix plus the totals of the waves before this
+// one; `total` = the block's sum.  ws: THREADS / 64 words of LDS -- a caller
+// that calls again puts a barrier of its own before ws is rewritten.
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_excl_prefix(uint32_t v, uint32_t *ws, uint32_t &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t incl = wave_incl_sum(v);
+    if (lane == 63)
+        ws[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) {
+        const uint32_t t = ws[w];
+        before += w < wave ? t : 0u;
+        all += t;
+    }
+    total = all;
+    return before + incl - v;
+}
+
+// counts[0 .. total) -> exclusive offsets, in place, by ONE workgroup of
+// THREADS threads: PER consecutive counts per thread and iteration (an
+// iteration's sum must fit 32 bits), with a 64-bit running total that is the
+// same in every thread and is returned.  each(i, offset) runs for every
+// element, in the thread that writes it.  ws: THREADS / 64 words of LDS.
+template <int THREADS, int PER, typename F>
+__device__ __forceinline__ uint64_t block_scan_counts(uint32_t *__restrict__ counts, uint32_t total,
+                                                      uint32_t *ws, F each)
+{
+    uint64_t carry = 0;
+    for (uint32_t at = 0; at < total; at += THREADS * PER) {
+        const uint32_t i0 = at + PER * threadIdx.x; // this thread's run of counts
+        uint32_t v[PER], sum = 0;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            v[k] = i0 + k < total ? counts[i0 + k] : 0u;
+            sum += v[k];
+        }
+        uint32_t all;
+        uint64_t excl = carry + block_excl_prefix<THREADS>(sum, ws, all);
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            if (i0 + k < total) {
+                counts[i0 + k] = (uint32_t)excl;
+                each(i0 + k, excl);
+            }
+            excl += v[k];
+        }
+        carry += all;
+        __syncthreads(); // ws is rewritten by the next iteration
+    }
+    return carry;
+}
+
 __device__ __forceinline__ uint32_t mbcnt64(uint64_t m)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),

@@ -201,47 +201,17 @@ k_rxdemux_scan(uint32_t *__restrict__ counts, uint32_t nblocks, uint32_t ns,
 {
     __shared__ uint32_t ws[kDmxScan / 64];
     __shared__ unsigned long long unbound;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t total = (ns + 1u) * nblocks; // <= 255 * 2^20
-    uint64_t carry = 0; // the same in every thread
-    for (uint32_t at = 0; at < total; at += kDmxScan * kDmxScanPer) {
-        const uint32_t i0 = at + kDmxScanPer * threadIdx.x; // this thread's run of counts
-        uint32_t v[kDmxScanPer], sum = 0;
-#pragma unroll
-        for (int k = 0; k < kDmxScanPer; ++k) {
-            v[k] = i0 + k < total ? counts[i0 + k] : 0u;
-            sum += v[k];
-        }
-        const uint32_t incl = wave_incl_sum(sum);
-        if (lane == 63)
-            ws[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0; // (<= 4096 counts of <= 4096 frames each: no wrap)
-#pragma unroll
-        for (int w = 0; w < kDmxScan / 64; ++w) {
-            const uint32_t t = ws[w];
-            before += w < wave ? t : 0u;
-            all += t;
-        }
-        uint64_t excl = carry + before + incl - sum;
-#pragma unroll
-        for (int k = 0; k < kDmxScanPer; ++k) {
-            const uint32_t i = i0 + k;
-            if (i < total) {
-                counts[i] = (uint32_t)excl;
-                const uint32_t row = i / nblocks;
-                if (i == row * nblocks) {
-                    if (row < ns)
-                        start[row] = excl;
-                    else
-                        unbound = excl;
-                }
+    // (<= 4096 counts of <= 4096 frames each per iteration: no wrap)
+    const uint64_t carry = block_scan_counts<kDmxScan, kDmxScanPer>(
+        counts, (ns + 1u) * nblocks /* <= 255 * 2^20 */, ws, [&](uint32_t i, uint64_t excl) {
+            const uint32_t row = i / nblocks;
+            if (i == row * nblocks) { // a row's first count
+                if (row < ns)
+                    start[row] = excl;
+                else
+                    unbound = excl;
             }
-            excl += v[k];
-        }
-        carry += all;
-        __syncthreads(); // ws is rewritten by the next iteration
-    }
+        });
     if (threadIdx.x >= ns && threadIdx.x < kDmxStarts - 1u)
         start[threadIdx.x] = unbound;
     if (threadIdx.x == kDmxStarts - 1u)
@@ -284,19 +254,10 @@ k_rxdemux_scatter(const uint8_t *__restrict__ sock, uint64_t n, uint32_t ns,
         for (int w = 0; w < kDmxWaves; ++w)
             tot += run_all[256u * w + c];
     }
-    const uint32_t incl = wave_incl_sum(tot);
-    if (lane == 63)
-        ws[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kDmxWaves; ++w) {
-        const uint32_t x = ws[w];
-        before += w < wave ? x : 0u;
-        total += x;
-    }
+    uint32_t total;
+    const uint32_t first = block_excl_prefix<kDmxThreads>(tot, ws, total);
     if (own) {
-        uint32_t at = before + incl - tot;
+        uint32_t at = first;
         lbase[c] = at;
         goff[c] = class_counted(c, ns) ? offsets[(size_t)(c < ns ? c : ns) * nblocks + blockIdx.x]
                                        : 0u;

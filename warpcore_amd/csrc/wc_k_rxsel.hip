@@ -63,27 +63,6 @@ __device__ __forceinline__ uint32_t sel_lane(const uint8_t *verdict, uint64_t n,
     return sel_match(d, mask, first, n);
 }
 
-// Block-wide exclusive prefix of v (every thread of the block calls it):
-// the DPP wave prefix plus the totals of the waves before this one; `total`
-// = the block's sum.  ws: kSelThreads / 64 words of LDS.
-__device__ __forceinline__ uint32_t sel_block_prefix(uint32_t v, uint32_t *ws, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_sum(v);
-    if (lane == 63)
-        ws[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kSelThreads / 64; ++w) {
-        const uint32_t t = ws[w];
-        before += w < wave ? t : 0u;
-        all += t;
-    }
-    total = all;
-    return before + incl - v;
-}
-
 __global__ void __launch_bounds__(kSelThreads)
 k_rxsel_count(const uint8_t *__restrict__ verdict, uint64_t n, uint32_t mask, uint64_t nchunks,
               uint32_t *__restrict__ counts)
@@ -92,7 +71,7 @@ k_rxsel_count(const uint8_t *__restrict__ verdict, uint64_t n, uint32_t mask, ui
     int64_t first;
     const uint32_t m = sel_lane(verdict, n, mask, nchunks, first);
     uint32_t total;
-    (void)sel_block_prefix((uint32_t)__builtin_popcount(m), ws, total);
+    (void)block_excl_prefix<kSelThreads>((uint32_t)__builtin_popcount(m), ws, total);
     if (threadIdx.x == 0)
         counts[blockIdx.x] = total;
 }
@@ -102,27 +81,9 @@ __global__ void __launch_bounds__(kSelScan)
 k_rxsel_scan(uint32_t *__restrict__ counts, uint32_t nblocks, unsigned long long *__restrict__ count)
 {
     __shared__ uint32_t ws[kSelScan / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t carry = 0; // the same in every thread
-    for (uint32_t at = 0; at < nblocks; at += kSelScan) {
-        const uint32_t i = at + threadIdx.x;
-        const uint32_t v = i < nblocks ? counts[i] : 0u;
-        const uint32_t incl = wave_incl_sum(v);
-        if (lane == 63)
-            ws[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0; // (<= 1024 blocks x 4096 matches: no wrap)
-#pragma unroll
-        for (int w = 0; w < kSelScan / 64; ++w) {
-            const uint32_t t = ws[w];
-            before += w < wave ? t : 0u;
-            all += t;
-        }
-        if (i < nblocks)
-            counts[i] = (uint32_t)(carry + before + incl - v);
-        carry += all;
-        __syncthreads(); // ws is rewritten by the next iteration
-    }
+    // (<= 1024 blocks x 4096 matches per iteration: no wrap)
+    const uint64_t carry =
+        block_scan_counts<kSelScan, 1>(counts, nblocks, ws, [](uint32_t, uint64_t) {});
     if (threadIdx.x == 0)
         *count = carry;
 }
@@ -136,7 +97,7 @@ k_rxsel_scatter(const uint8_t *__restrict__ verdict, uint64_t n, uint32_t mask, 
     int64_t first;
     uint32_t m = sel_lane(verdict, n, mask, nchunks, first);
     uint32_t total;
-    uint32_t r = sel_block_prefix((uint32_t)__builtin_popcount(m), ws, total);
+    uint32_t r = block_excl_prefix<kSelThreads>((uint32_t)__builtin_popcount(m), ws, total);
     while (m) { // r + popcount(m) <= total <= kSelBlock * 16
         idx[r++] = (uint32_t)(first + __builtin_ctz(m));
         m &= m - 1u;

@@ -376,6 +376,13 @@ void load_config_locked();
 int init_locked(int device, Device **out);
 // The device-resident batch calls' entry (see wc_rt_config.cpp).
 int ensure_device(Device **out, Config *cfg);
+// Its results as one object, after the argument checks:
+// `Ready R; if (R.rc) return R.rc;` -- D and C are valid where rc is WC_OK.
+struct Ready {
+    Device *D = nullptr;
+    Config C;
+    const int rc = ensure_device(&D, &C);
+};
 
 // --- wc_rt_plan.cpp -----------------------------------------------------------
 struct Plan {
@@ -397,6 +404,14 @@ int run(const Device &D, const Config &C, const wc::LaunchArgs &args, const Plan
 hipError_t rx_launch(Device &D, const Config &C, const void *base, const uint64_t *offs,
                      const uint16_t *flens, uint64_t n, uint8_t *verdict, uint64_t *drops,
                      hipStream_t st, void *rec = nullptr);
+// The drops among n verdict bytes in host memory (the host RX calls' *h_drops).
+inline uint64_t rx_count_drops(const uint8_t *v, uint64_t n)
+{
+    uint64_t drops = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        drops += WC_RX_IS_DROP(v[i]);
+    return drops;
+}
 
 // --- wc_rt_server.cpp ---------------------------------------------------------
 constexpr int kSrvFallback = 1; // serve_batch: not served, take the launch path

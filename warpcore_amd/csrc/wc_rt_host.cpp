@@ -793,12 +793,8 @@ int wc_rx_verdict_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
     if (n && !h_verdict)
         return WC_EINVAL;
     const int rc = host_batch(h_base, h_bytes, h_off, h_frame_len, n, {{h_verdict}}, kKindRx);
-    if (rc == WC_OK && h_drops) {
-        uint64_t d = 0;
-        for (uint64_t i = 0; i < n; ++i)
-            d += WC_RX_IS_DROP(h_verdict[i]);
-        *h_drops = d;
-    }
+    if (rc == WC_OK && h_drops)
+        *h_drops = rx_count_drops(h_verdict, n);
     return rc;
 }
 

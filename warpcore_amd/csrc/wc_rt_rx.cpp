@@ -115,12 +115,10 @@ int wc_rx_verdict_ragged(const void *d_base, const uint64_t *d_off, const uint16
         return WC_OK;
     if (!d_base || !d_off || !d_frame_len || !d_verdict)
         return WC_EINVAL;
-    Device *D = nullptr;
-    Config C;
-    int rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
-    return hip_err(rx_launch(*D, C, d_base, d_off, d_frame_len, n, d_verdict, d_drops,
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    return hip_err(rx_launch(*R.D, R.C, d_base, d_off, d_frame_len, n, d_verdict, d_drops,
                              (hipStream_t)stream));
 }
 
@@ -132,17 +130,16 @@ uint64_t wc_rx_select_scratch(uint64_t n)
 // Indices are uint32: a batch is at most 2^32 frames.
 static constexpr uint64_t kRxSelectMax = 1ull << 32;
 
-// *d_count = 0 for an empty batch (device memory: on the caller's stream).
-static int rx_count_zero(uint64_t *d_count, void *stream)
+// An empty batch: `bytes` zero bytes at d_out (NULL: nothing to write) --
+// device memory, so on the caller's stream.
+static int rx_zero_empty(void *d_out, size_t bytes, void *stream)
 {
-    if (!d_count)
+    if (!d_out)
         return WC_OK;
-    Device *D = nullptr;
-    Config C;
-    int rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
-    return hip_err(hipMemsetAsync(d_count, 0, sizeof(uint64_t), (hipStream_t)stream));
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    return hip_err(hipMemsetAsync(d_out, 0, bytes, (hipStream_t)stream));
 }
 
 int wc_rx_select(const uint8_t *d_verdict, uint64_t n, uint32_t mask, uint32_t *d_list,
@@ -151,14 +148,12 @@ int wc_rx_select(const uint8_t *d_verdict, uint64_t n, uint32_t mask, uint32_t *
     if (n > kRxSelectMax)
         return WC_EINVAL;
     if (n == 0)
-        return rx_count_zero(d_count, stream);
+        return rx_zero_empty(d_count, sizeof(uint64_t), stream);
     if (!d_verdict || !d_list || !d_count || !d_scratch || ((uintptr_t)d_scratch & 3u))
         return WC_EINVAL;
-    Device *D = nullptr;
-    Config C;
-    int rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
+    Ready R;
+    if (R.rc)
+        return R.rc;
     return hip_err(wc::launch_rx_select(d_verdict, n, mask, d_list, d_count, d_scratch,
                                         (hipStream_t)stream));
 }
@@ -172,17 +167,15 @@ int wc_rx_deliver_ragged(const void *d_base, const uint64_t *d_off, const uint16
     if (n > kRxSelectMax || (d_list != nullptr) != (d_count != nullptr))
         return WC_EINVAL;
     if (n == 0)
-        return rx_count_zero(d_count, stream);
+        return rx_zero_empty(d_count, sizeof(uint64_t), stream);
     if (!d_base || !d_off || !d_frame_len || !d_verdict || !d_rec || ((uintptr_t)d_rec & 15u))
         return WC_EINVAL;
     if (d_list && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
         return WC_EINVAL;
-    Device *D = nullptr;
-    Config C;
-    int rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
-    hipError_t e = rx_launch(*D, C, d_base, d_off, d_frame_len, n, d_verdict, d_drops,
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    hipError_t e = rx_launch(*R.D, R.C, d_base, d_off, d_frame_len, n, d_verdict, d_drops,
                              (hipStream_t)stream, d_rec);
     if (e == hipSuccess && d_list)
         e = wc::launch_rx_select(d_verdict, n, WC_RX_MASK_DELIVER, d_list, d_count, d_scratch,
@@ -210,19 +203,17 @@ int wc_rx_deliver_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_o
                               {{h_verdict, (uint8_t *)h_rec}}, kKindRxDeliver);
     if (rc != WC_OK)
         return rc;
-    // The list and the drop count by the calling thread, once the batch has
-    // drained: one pass over n bytes (the frames are in host memory anyway).
-    uint64_t drops = 0, cnt = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint8_t v = h_verdict[i];
-        drops += WC_RX_IS_DROP(v);
-        if (h_list && (v == WC_RX_OK || v == WC_RX_OK_NO_CKSUM))
-            h_list[cnt++] = (uint32_t)i;
-    }
-    if (h_count)
-        *h_count = cnt;
+    // The drop count and the list by the calling thread, once the batch has
+    // drained: a pass each over n bytes (the frames are in host memory anyway).
     if (h_drops)
-        *h_drops = drops;
+        *h_drops = rx_count_drops(h_verdict, n);
+    if (h_list) {
+        uint64_t cnt = 0;
+        for (uint64_t i = 0; i < n; ++i)
+            if (h_verdict[i] == WC_RX_OK || h_verdict[i] == WC_RX_OK_NO_CKSUM)
+                h_list[cnt++] = (uint32_t)i;
+        *h_count = cnt;
+    }
     return WC_OK;
 }
 
@@ -313,27 +304,16 @@ int wc_rx_demux(const void *d_base, const uint64_t *d_off, const struct wc_rx_re
 {
     if (n > kRxSelectMax || ns > tab::kTabMaxSocks || (d_list != nullptr) != (d_start != nullptr))
         return WC_EINVAL;
-    if (n == 0) {
-        if (!d_start)
-            return WC_OK;
-        Device *D = nullptr;
-        Config C;
-        const int rc = ensure_device(&D, &C);
-        if (rc)
-            return rc;
-        return hip_err(hipMemsetAsync(d_start, 0, kRxStarts * sizeof(uint64_t),
-                                      (hipStream_t)stream));
-    }
+    if (n == 0)
+        return rx_zero_empty(d_start, kRxStarts * sizeof(uint64_t), stream);
     if (!d_base || !d_off || !d_rec || ((uintptr_t)d_rec & 15u) || !d_tab ||
         ((uintptr_t)d_tab & 3u) || !d_sock)
         return WC_EINVAL;
     if (d_list && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
         return WC_EINVAL;
-    Device *D = nullptr;
-    Config C;
-    const int rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
+    Ready R;
+    if (R.rc)
+        return R.rc;
     return hip_err(wc::launch_rx_demux(d_base, d_off, d_rec, n, d_tab, ns, d_sock, d_list, d_start,
                                        d_scratch, (hipStream_t)stream));
 }
@@ -358,12 +338,8 @@ int wc_rx_demux_host(const void *h_base, uint64_t h_bytes, const uint64_t *h_off
                               {{h_verdict, (uint8_t *)h_rec, h_sock}}, kKindRxDemux, h_tab, ns);
     if (rc != WC_OK)
         return rc;
-    if (h_drops) {
-        uint64_t drops = 0;
-        for (uint64_t i = 0; i < n; ++i)
-            drops += WC_RX_IS_DROP(h_verdict[i]);
-        *h_drops = drops;
-    }
+    if (h_drops)
+        *h_drops = rx_count_drops(h_verdict, n);
     if (!h_list)
         return WC_OK;
     // The per-socket runs by the calling thread: one counting pass over the n

@@ -14,6 +14,22 @@
 
 using namespace wc::rt;
 
+// The stores of mk_ip4_hdr and udp_tx (ip4.c:184-186, udp.c:209-213) into one
+// frame, by its seal status: a frame that has one up to WC_TX_IP_ONLY is IPv4
+// or IPv6 with its header inside it, so its EtherType and IHL bytes are there
+// to find the fields by; any other frame is left as it is.
+static void tx_store_sums(uint8_t *frame, uint8_t status, uint16_t iph, uint16_t udp)
+{
+    if (status > WC_TX_IP_ONLY)
+        return;
+    uint8_t *ip = frame + 14;
+    const bool v4 = ip[-2] == 0x08; // 0x0800, else 0x86DD
+    if (v4)
+        memcpy(ip + 10, &iph, 2);
+    if (status != WC_TX_IP_ONLY)
+        memcpy(ip + (v4 ? (ip[0] & 15u) * 4u : 40u) + 6, &udp, 2);
+}
+
 extern "C" {
 
 int wc_tx_seal_ragged(void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
@@ -28,15 +44,13 @@ int wc_tx_seal_ragged(void *d_base, const uint64_t *d_off, const uint16_t *d_fra
         return WC_EINVAL;
     if (!d_base || !d_off || !d_frame_len || !d_status)
         return WC_EINVAL;
-    Device *D = nullptr;
-    Config C;
-    int rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
+    Ready R;
+    if (R.rc)
+        return R.rc;
     static_assert(WC_TX_ZERO_UDP_CKSUM == wc::kTxZeroUdp && WC_TX_NO_STORE == wc::kTxNoStore,
                   "the kernel's flags are the ABI's");
     return hip_err(wc::launch_tx_seal(d_base, d_off, d_frame_len, n, flags, d_status,
-                                      d_out_ip_hdr, d_out_udp, d_errors, C.nt != 0,
+                                      d_out_ip_hdr, d_out_udp, d_errors, R.C.nt != 0,
                                       (hipStream_t)stream));
 }
 
@@ -64,23 +78,10 @@ int wc_tx_seal_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off,
                               {{(uint8_t *)udp, (uint8_t *)iph, h_status}},
                               zero_udp ? kKindTxZero : kKindTx);
     if (rc == WC_OK) {
-        // The stores of mk_ip4_hdr and udp_tx (ip4.c:184-186, udp.c:209-213),
-        // by the status: a frame that has one is IPv4 or IPv6 with its header
-        // inside it, so its EtherType and IHL bytes are there to find the
-        // fields by.
-        uint8_t *hb = (uint8_t *)h_base;
         uint64_t errs = 0;
         for (uint64_t i = 0; i < n; ++i) {
-            const uint8_t s = h_status[i];
-            errs += WC_TX_IS_ERROR(s);
-            if (s > WC_TX_IP_ONLY)
-                continue;
-            uint8_t *ip = hb + h_off[i] + 14;
-            const bool v4 = ip[-2] == 0x08; // 0x0800, else 0x86DD
-            if (v4)
-                memcpy(ip + 10, &iph[i], 2);
-            if (s != WC_TX_IP_ONLY)
-                memcpy(ip + (v4 ? (ip[0] & 15u) * 4u : 40u) + 6, &udp[i], 2);
+            errs += WC_TX_IS_ERROR(h_status[i]);
+            tx_store_sums((uint8_t *)h_base + h_off[i], h_status[i], iph[i], udp[i]);
         }
         if (h_errors)
             *h_errors = errs;
@@ -140,17 +141,16 @@ int wc_tx_build_ragged(void *d_base, const uint64_t *d_off, const struct wc_tx_d
         return WC_EINVAL;
     if ((flags & WC_TX_NO_STORE) && (!d_out_ip_hdr || !d_out_udp))
         return WC_EINVAL;
-    int rc = tx_build_args(d_base, d_off, d_desc, d_socks, ns, d_dsts, ndst, d_frame_len, d_status);
+    const int rc =
+        tx_build_args(d_base, d_off, d_desc, d_socks, ns, d_dsts, ndst, d_frame_len, d_status);
     if (rc)
         return rc;
-    Device *D = nullptr;
-    Config C;
-    rc = ensure_device(&D, &C);
-    if (rc)
-        return rc;
+    Ready R;
+    if (R.rc)
+        return R.rc;
     return hip_err(wc::launch_tx_build(d_base, d_off, d_desc, n, d_socks, ns, d_dsts, ndst,
                                        slot_bytes, flags, d_frame_len, d_status, d_out_ip_hdr,
-                                       d_out_udp, d_errors, C.nt != 0, (hipStream_t)stream));
+                                       d_out_udp, d_errors, R.C.nt != 0, (hipStream_t)stream));
 }
 
 namespace {
@@ -253,17 +253,14 @@ int wc_tx_build_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off,
         rc = host_batch(h_base, h_bytes, off, len, nb, {{(uint8_t *)udp, (uint8_t *)iph, st}},
                         zero_udp ? kKindTxZero : kKindTx);
         // The two stores, as wc_tx_seal_host makes them: every frame here is one
-        // the seal's chain accepts (its status is the build's).
+        // the seal's chain accepts (its status is the build's), and its IHL
+        // says the 20 bytes the build wrote.
         for (k = 0; rc == WC_OK && k < nb; ++k) {
-            uint8_t *ip = hb + off[k] + 14;
-            const bool v4 = ip[-2] == 0x08;
             if (st[k] > WC_TX_SEALED_ZERO_UDP) {
                 rc = WC_EINVAL; // (cannot happen: the headers above are the chain's)
                 break;
             }
-            if (v4)
-                memcpy(ip + 10, &iph[k], 2);
-            memcpy(ip + (v4 ? 20u : 40u) + 6, &udp[k], 2);
+            tx_store_sums(hb + off[k], st[k], iph[k], udp[k]);
         }
     }
     if (rc == WC_OK && h_errors)
