@@ -450,6 +450,159 @@ int wc_tx_build_host(void *h_base, uint64_t h_bytes, const uint64_t *h_off, cons
                      const struct wc_tx_dst *h_dsts, uint32_t ndst, uint32_t slot_bytes, uint32_t flags,
                      uint16_t *h_frame_len, uint8_t *h_status, uint64_t *h_errors);
 
+/* --- RX replies: ICMP verdicts, echo and unreachable frames --------------- */
+
+/* What the reference's RX path does with a frame beyond delivering it: the
+ * MAC filter of eth_rx (eth.c:65-73), the address filter of ip4_rx / ip6_rx
+ * (is_my_ip4 / is_my_ip6), the ICMP / ICMPv6 checksum verdict (icmp4.c:153-160,
+ * icmp6.c:259-267), the echo replies (icmp4_tx / icmp6_tx) and the protocol
+ * and port unreachables (ip4.c:133-137, udp.c:147-155).  All of it is a
+ * function of the frame bytes and the engine table below; what changes engine
+ * state (ARP, neighbour discovery) is handed to the host as WC_RR_HOST. */
+#define WC_RX_MAX_IFADDR 16
+struct wc_rx_ifaddr {     /* 52 bytes: one w_ifaddr (warpcore.h), as is_my_ip4 / is_my_ip6 read it */
+    uint8_t af;           /* 4 or 6 */
+    uint8_t pad[3];       /* ignored */
+    uint8_t addr[16];     /* af 4: bytes 0..3 count, as in struct wc_rx_sock */
+    uint8_t bcast[16];    /* af 4: bcast4 in bytes 0..3; af 6: bcast6 */
+    uint8_t snma[16];     /* af 6: snma6; ignored for af 4 */
+};
+struct wc_rx_engine {     /* 844 bytes, little-endian, what the RX path reads of a w_engine */
+    uint8_t  mac[6];      /* w->mac */
+    uint16_t mtu;         /* w->mtu */
+    uint32_t naddr;       /* <= WC_RX_MAX_IFADDR */
+    struct wc_rx_ifaddr addr[WC_RX_MAX_IFADDR];
+};
+
+/* Pure host arithmetic (no GPU, no library state), like wc_tx_socks_check:
+ * WC_EINVAL for a NULL pointer, naddr > 16, an af other than 4 / 6 among the
+ * first naddr entries, an af-6 entry after an af-4 entry (backend_addr_config
+ * lays them out IPv6 first, ifaddr.c:94-146, and the reply sources depend on
+ * it), or mtu < 68 -- the reference has no such rule, but its w->mtu -
+ * sizeof(*src_ip) (icmp6.c:164) wraps below 40; else WC_OK.  The reply sources
+ * are the first af-4 entry for IPv4 (ifaddr[addr4_pos], ip4.c:180) and entry
+ * 0 for IPv6 (ip6.c:155). */
+int wc_rx_engine_check(const struct wc_rx_engine *e);
+
+enum wc_rx_reply_action {        /* uint8, all < 32 so wc_rx_select masks apply */
+    WC_RR_NONE = 0,              /* nothing to send, nothing for the host */
+    WC_RR_HOST = 1,              /* the host's: changes engine state (ARP; ICMPv6 NSOL / NADV, checksum verified) */
+    WC_RR_FILTERED = 2,          /* MAC or IP destination is not ours (eth.c:65-73, ip4.c:103-108, ip6.c:98-103) */
+    WC_RR_ICMP_BAD_CKSUM = 3,    /* icmp4.c:156, icmp6.c:263: dropped */
+    WC_RR_MALFORMED = 4,         /* a length the reference would wrap, or a byte it would read past the frame: no reply */
+    WC_RR_NO_ROOM = 5,           /* the reply is longer than slot_bytes: no reply */
+    WC_RR_ECHO4 = 8, WC_RR_ECHO6 = 9,
+    WC_RR_UNREACH_PORT4 = 10, WC_RR_UNREACH_PORT6 = 11, WC_RR_UNREACH_PROTO4 = 12,
+};
+#define WC_RR_MASK_REPLY (0x1F00u)
+
+/* Behind a wc_rx_verdict_ragged / wc_rx_deliver_ragged (and optionally a
+ * wc_rx_demux) of the same frames on the same stream: it reads their
+ * d_verdict and d_sock (optional) and does not decide again what they decided.
+ * d_action[i] = frame i's enum wc_rx_reply_action code, d_reply_len[i] = the
+ * reply's frame length for a reply action, else 0.  d_eng: the table in device
+ * memory.  With d_list / d_count (both or neither: checked first, for every
+ * n): wc_rx_select(d_action, n, WC_RR_MASK_REPLY, ...) on the same stream,
+ * with d_scratch of wc_rx_select_scratch(n) bytes.
+ *
+ * The chain, in the reference's order; the first hit names the code.  "ip" is
+ * the frame from byte 14, hl = 4 * IHL as the byte gives it (values below 20
+ * included, as the reference would use them) or 40, flen the frame length;
+ * lengths are computed in 32 bits unless a wrap is named.
+ *   1. The verdict is a drop (WC_RX_IS_DROP) or above 9:            NONE.
+ *   2. Frame bytes 0..5 differ from mac and from ff x 6, and bytes 0..1 are
+ *      not 33 33 (eth.c:65-67):                                     FILTERED.
+ *   3. Verdict NOT_IP:                                              HOST.
+ *   4. IPv4: for no af-4 entry is dst equal to addr, bcast or 255.255.255.255
+ *      (is_my_ip4 with match_bcast; with no af-4 entry nothing matches);
+ *      IPv6: for no af-6 entry is dst equal to addr, snma or bcast:  FILTERED.
+ *      One deliberate difference: the reference's IPv6 loop (ip6.c:173-187)
+ *      also compares against the 16 union bytes of IPv4 entries; the plan
+ *      compares af-6 entries only.
+ *   5. Verdict OK / OK_NO_CKSUM: NONE unless d_sock is given and d_sock[i] ==
+ *      WC_RX_SOCK_UNBOUND and the frame's SOURCE address is an addr of its
+ *      family in the table (no broadcast match) -- udp.c:150-153 as it stands;
+ *      then UNREACH_PORT4 with reply length 50 + hl, or UNREACH_PORT6 with
+ *      reply length 110 (its ICMP data is 48 bytes from frame byte 54 on:
+ *      ip6_data(buf), icmp6.c:163, 210); flen < 102 is MALFORMED.
+ *   6. Verdict NOT_UDP, IPv4, protocol != 1: UNREACH_PROTO4, reply length 50 +
+ *      hl; it copies hl + 8 bytes from ip, flen < 14 + hl + 8 is MALFORMED.
+ *   7. Verdict NOT_UDP, IPv4, protocol 1: icmp_len = MIN((ip_len - hl) &
+ *      0xFFFF, flen - 14 - hl); ip_cksum(ip + hl, icmp_len) != 0 (a zero
+ *      length sums to 0xFFFF) is ICMP_BAD_CKSUM; a type other than 8 is NONE;
+ *      for type 8, with t = MIN(ip_len, mtu): t < hl + 8 is MALFORMED (the
+ *      uint16 wrap of icmp4.c:91), 14 + t > flen is MALFORMED (the reference
+ *      copies its neighbour's bytes), else ECHO4 with data_len = t - hl - 8
+ *      and reply length 42 + data_len.
+ *   8. Verdict NOT_UDP, IPv6, next header != 58:                    NONE.
+ *   9. Verdict NOT_UDP, IPv6, next header 58: icmp_len = MIN(ip6_len, flen -
+ *      54); payload_cksum(ip, icmp_len + 40) != 0 is ICMP_BAD_CKSUM; flen < 55
+ *      (no type byte) is MALFORMED; types 135 / 136 are HOST; for type 128,
+ *      with t = MIN(ip6_len, mtu - 40): t < 8 is MALFORMED (icmp6.c:202), 54 +
+ *      t > flen is MALFORMED, else ECHO6 with data_len = t - 8 and reply
+ *      length 62 + data_len; any other type is NONE.
+ *  10. A reply longer than slot_bytes:                              NO_ROOM.
+ * n = 0 is WC_OK, writes *d_count = 0 where given and looks at no other
+ * pointer.  WC_EINVAL: n > 2^32, slot_bytes > 65535, a NULL d_base / d_off /
+ * d_frame_len / d_verdict / d_eng / d_action / d_reply_len, d_eng not 4-byte
+ * aligned, a list without a 4-byte-aligned d_scratch.  Asynchronous on
+ * `stream`: one launch, four with the list; no library lock, no atomic, no
+ * wait between workgroups, and the same input gives the same output.  No byte
+ * outside a frame is read (reads are the aligned 16-byte chunks that overlap
+ * it). */
+int wc_rx_reply_plan(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                     const uint8_t *d_verdict, const uint8_t *d_sock /* optional */,
+                     const struct wc_rx_engine *d_eng, uint32_t slot_bytes,
+                     uint8_t *d_action, uint16_t *d_reply_len,
+                     uint32_t *d_list, uint64_t *d_count, void *d_scratch, void *stream);
+
+/* Reply j, for j < MIN(*d_count, m), answers frame d_list[j]: it is written
+ * at d_out_base + d_out_off[j], may use slot_bytes bytes there, and
+ * d_out_len[j] is its length.  For every other j < m d_out_len[j] = 0 and the
+ * slot is untouched (the reference's "no more bufs; ICMP not sent").
+ * *d_built is written, not accumulated: the number of j with a non-zero
+ * length.  *d_count is read on the device: one launch, no host
+ * synchronisation.  The build derives every length and bound again from the
+ * frame -- the MALFORMED / NO_ROOM conditions above, that the header bytes a
+ * reply reads lie inside the frame (flen >= 34 / 54), a list index >= n, an
+ * action that is no reply action -- and writes length 0 and touches nothing
+ * where they fail, so a stale action byte cannot make it read or write out of
+ * range.  It does not verify checksums or filters again.  RX frames and reply
+ * slots must not overlap, nor reply slots each other (they may share 16-byte
+ * chunks and cache lines, as in the TX build); no byte outside [slot, slot +
+ * reply length) is written, none outside the source frame read (reads are
+ * aligned dwords inside the 16-byte chunks that overlap it).
+ *   Ethernet: dst = the request's bytes 6..11, src = mac, type 08 00 / 86 dd.
+ *   IPv4 (mk_ip4_hdr(v, 0), v->flags = 0): 45 00, total length reply length -
+ *     14, d_ip_id[j] as stored (00 00 when d_ip_id is NULL; the reference
+ *     draws it at random, ip4.c:167-168), 40 00, ff, 01, ip_cksum of the 20
+ *     bytes, src = the first af-4 address, dst = the request's IP source.
+ *   ICMP: ECHO4 00 00, checksum, the request's ICMP bytes 4..7, then request
+ *     bytes [14 + hl + 8, 14 + t); UNREACH_PORT4 03 03, checksum, four zero
+ *     bytes, then request bytes [14, 14 + hl + 8); UNREACH_PROTO4 03 02, then
+ *     the same.  Checksum: ip_cksum(icmp, 8 + data_len) with the field taken
+ *     as 0, stored raw.
+ *   IPv6 (mk_ip6_hdr(v, 0)): first word 60 00 00 00, written whole (the same
+ *     deliberate difference from the reference's OR as in the TX build),
+ *     payload length reply length - 54, 3a, ff, src = entry 0's address, dst
+ *     = the request's source.
+ *   ICMPv6: ECHO6 81 00, checksum, the request's bytes 58..61, then request
+ *     bytes [62, 54 + t); UNREACH_PORT6 01 04, checksum, four zero bytes, then
+ *     request bytes [54, 102).  Checksum: payload_cksum(ip, reply length - 14)
+ *     with the field taken as 0, stored raw.
+ * m = 0 is WC_OK, writes *d_built = 0 and looks at no other pointer; n = 0
+ * writes that and m zero lengths.  WC_EINVAL: n > 2^32, slot_bytes > 65535, a
+ * NULL d_built, a NULL d_out_len with m > 0; with m > 0 and n > 0 any other
+ * NULL pointer but d_ip_id, or d_eng not 4-byte aligned.  The only atomic is
+ * the built count's, one per workgroup of a grid no larger than the device
+ * holds at once. */
+int wc_rx_reply_build(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                      const uint8_t *d_action, const uint32_t *d_list, const uint64_t *d_count,
+                      const struct wc_rx_engine *d_eng,
+                      void *d_out_base, const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
+                      const uint16_t *d_ip_id /* optional, m entries */,
+                      uint16_t *d_out_len, uint64_t *d_built, void *stream);
+
 /* --- host-memory batch (end-to-end: pinned H2D, kernel, D2H) ------------- */
 
 /* Same as wc_cksum_ragged, but every buffer is host memory: packet i is

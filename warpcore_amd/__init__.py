@@ -21,6 +21,10 @@ from .cksum import (KIND_IP, KIND_PAYLOAD, SclkProbe, WcError, cksum_host, cksum
                     rx_socktab_bytes, rx_socktab_build, rx_socktab_lookup, rx_demux,
                     rx_demux_host, rx_demux_scratch, RX_SOCK, RX_SOCK_NONE, RX_SOCK_UNBOUND,
                     RX_DEMUX_MAX_SOCKS,
+                    rx_engine_check, rx_reply_plan, rx_reply_build, RX_IFADDR, RX_ENGINE,
+                    RX_MAX_IFADDR, RR_NAMES, RR_MASK_REPLY, RR_NONE, RR_HOST, RR_FILTERED,
+                    RR_ICMP_BAD_CKSUM, RR_MALFORMED, RR_NO_ROOM, RR_ECHO4, RR_ECHO6,
+                    RR_UNREACH_PORT4, RR_UNREACH_PORT6, RR_UNREACH_PROTO4,
                     tx_seal_ragged, tx_seal_host, TX_NAMES, TX_ERRORS,
                     TX_SEALED, TX_SEALED_ZERO_UDP, TX_IP_ONLY, TX_NOT_UDP, TX_NOT_IP,
                     TX_BAD_VERSION, TX_MALFORMED, TX_TRUNCATED,
@@ -42,6 +46,10 @@ __all__ = [
     "RX_MASK_DELIVER", "RX_MASK_HOST",
     "rx_socktab_bytes", "rx_socktab_build", "rx_socktab_lookup", "rx_demux", "rx_demux_host",
     "rx_demux_scratch", "RX_SOCK", "RX_SOCK_NONE", "RX_SOCK_UNBOUND", "RX_DEMUX_MAX_SOCKS",
+    "rx_engine_check", "rx_reply_plan", "rx_reply_build", "RX_IFADDR", "RX_ENGINE",
+    "RX_MAX_IFADDR", "RR_NAMES", "RR_MASK_REPLY", "RR_NONE", "RR_HOST", "RR_FILTERED",
+    "RR_ICMP_BAD_CKSUM", "RR_MALFORMED", "RR_NO_ROOM", "RR_ECHO4", "RR_ECHO6",
+    "RR_UNREACH_PORT4", "RR_UNREACH_PORT6", "RR_UNREACH_PROTO4",
     "tx_seal_ragged", "tx_seal_host", "TX_NAMES", "TX_ERRORS", "TX_SEALED",
     "TX_SEALED_ZERO_UDP", "TX_IP_ONLY", "TX_NOT_UDP", "TX_NOT_IP", "TX_BAD_VERSION",
     "TX_MALFORMED", "TX_TRUNCATED",

@@ -653,6 +653,158 @@ def rx_demux_host(buf: np.ndarray, offsets: np.ndarray, frame_lens: np.ndarray,
 
 
 # --------------------------------------------------------------------------
+# RX replies (the filters, the ICMP checksum verdict, echo and unreachable
+# frames of eth_rx ... udp_rx / icmp*_rx).
+
+# struct wc_rx_ifaddr / wc_rx_engine (include/warpcore_gpu/wc_cksum.h)
+RX_MAX_IFADDR = 16
+RX_IFADDR = np.dtype([("af", "u1"), ("pad", "u1", 3), ("addr", "u1", 16), ("bcast", "u1", 16),
+                      ("snma", "u1", 16)])
+RX_ENGINE = np.dtype([("mac", "u1", 6), ("mtu", "<u2"), ("naddr", "<u4"),
+                      ("addr", RX_IFADDR, RX_MAX_IFADDR)])
+assert (RX_IFADDR.itemsize, RX_ENGINE.itemsize) == (52, 844)
+# enum wc_rx_reply_action
+RR_NONE, RR_HOST, RR_FILTERED, RR_ICMP_BAD_CKSUM, RR_MALFORMED, RR_NO_ROOM = range(6)
+RR_ECHO4, RR_ECHO6, RR_UNREACH_PORT4, RR_UNREACH_PORT6, RR_UNREACH_PROTO4 = range(8, 13)
+RR_MASK_REPLY = 0x1F00
+RR_NAMES = {RR_NONE: "none", RR_HOST: "host", RR_FILTERED: "filtered",
+            RR_ICMP_BAD_CKSUM: "icmp_bad_cksum", RR_MALFORMED: "malformed", RR_NO_ROOM: "no_room",
+            RR_ECHO4: "echo4", RR_ECHO6: "echo6", RR_UNREACH_PORT4: "unreach_port4",
+            RR_UNREACH_PORT6: "unreach_port6", RR_UNREACH_PROTO4: "unreach_proto4"}
+
+
+def rx_engine_check(engine: np.ndarray) -> None:
+    """``ValueError`` for an engine table wc_rx_engine_check refuses: more
+    than 16 addresses, an af other than 4 / 6, an IPv6 entry behind an IPv4
+    one, an MTU below 68.  No GPU."""
+    e = np.ascontiguousarray(engine, dtype=RX_ENGINE).reshape(-1)
+    if e.size != 1:
+        raise ValueError("one RX_ENGINE record")
+    rc = _lib.active().wc_rx_engine_check(e.ctypes.data)
+    if rc == _WC_EINVAL:
+        raise ValueError(f"RX engine table: at most {RX_MAX_IFADDR} addresses, af 4 or 6, the "
+                         "IPv6 entries first, mtu >= 68")
+    _check("wc_rx_engine_check", rc)
+
+
+def _engine_tensor(engine: torch.Tensor, device) -> None:
+    if not isinstance(engine, torch.Tensor) or not engine.is_cuda or engine.device != device:
+        raise ValueError(f"engine must be a device tensor on {device}")
+    if not engine.is_contiguous() or _nbytes(engine) != RX_ENGINE.itemsize:
+        raise ValueError(f"engine must be the contiguous {RX_ENGINE.itemsize} bytes of one RX_ENGINE")
+
+
+def _byte_array(name: str, t: torch.Tensor, n: int, device, size: int = 1) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+        raise ValueError(f"{name} must be a device tensor on {device}")
+    if t.element_size() != size or t.numel() < n or not t.is_contiguous() \
+            or t.is_floating_point():
+        raise ValueError(f"{name} must be a contiguous {size}-byte integer tensor of >= {n} entries")
+
+
+def rx_reply_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                  verdicts: torch.Tensor, sock: Optional[torch.Tensor], engine: torch.Tensor,
+                  slot_bytes: int, want_list: bool = True, stream=None, check: bool = True,
+                  out_list: Optional[torch.Tensor] = None,
+                  scratch: Optional[torch.Tensor] = None):
+    """What the reference's RX path does with every frame beyond delivering it
+    (wc_rx_reply_plan), behind an rx_verdict_ragged / rx_deliver_ragged (and
+    rx_demux) of the same frames whose ``verdicts`` and ``sock`` (may be None)
+    it reads.  ``engine``: a device tensor holding the bytes of one
+    ``RX_ENGINE`` record.  Returns ``(actions uint8 RR_*, reply_lens uint16,
+    list, count)``: ``list`` / ``count`` as rx_select gives them for
+    ``RR_MASK_REPLY`` (None, None with ``want_list=False``).  Asynchronous;
+    the scratch is allocated here unless given."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    d = base.device
+    _byte_array("verdicts", verdicts, n, d)
+    if sock is not None:
+        _byte_array("sock", sock, n, d)
+    _engine_tensor(engine, d)
+    if not 0 <= int(slot_bytes) <= 0xFFFF:
+        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
+    actions = torch.empty(n, dtype=torch.uint8, device=d)
+    reply_lens = torch.empty(n, dtype=torch.uint16, device=d)
+    lst = cnt = None
+    if want_list:
+        lst, own = _index_list(out_list, n, d)
+        cnt = torch.zeros(1, dtype=torch.int64, device=d)
+        if scratch is None:
+            scratch = _scratch(rx_select_scratch(n), d)
+        elif _nbytes(scratch) < rx_select_scratch(n) or scratch.device != d:
+            raise ValueError(f"scratch must hold rx_select_scratch(n) bytes on {d}")
+    with _on_device(d):
+        _check("wc_rx_reply_plan", _lib.active().wc_rx_reply_plan(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(verdicts),
+            sock.data_ptr() if sock is not None and n else None, engine.data_ptr(),
+            int(slot_bytes), actions.data_ptr() if n else None,
+            reply_lens.data_ptr() if n else None, lst.data_ptr() if want_list else None,
+            cnt.data_ptr() if want_list else None, scratch.data_ptr() if want_list else None,
+            _stream_ptr(stream, d)))
+    if want_list and own:
+        lst = lst[:n]
+    return actions, reply_lens, lst, cnt
+
+
+def rx_reply_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                   actions: torch.Tensor, reply_list: torch.Tensor, count: torch.Tensor,
+                   engine: torch.Tensor, out: torch.Tensor, out_offsets: torch.Tensor,
+                   slot_bytes: int, ip_ids: Optional[torch.Tensor] = None, stream=None,
+                   check: bool = True):
+    """Write the reply frames rx_reply_plan listed (wc_rx_reply_build): reply
+    ``j < min(count, m)``, ``m = out_offsets.numel()``, answers frame
+    ``reply_list[j]`` and is written at ``out[out_offsets[j]]``, at most
+    ``slot_bytes`` bytes.  ``out`` is a 1-byte device tensor that does not
+    overlap ``base``; ``ip_ids`` (optional) holds m uint16 ip->id values as
+    stored.  Returns ``(out_lens uint16 -- 0 where no reply was written --,
+    built)``, ``built`` a 1-element int64 device tensor.  ``count`` is read on
+    the device: no synchronisation.  ``check``: every frame inside ``base`` and
+    every slot inside ``out`` (one device reduction and a sync)."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    d = base.device
+    _same_device(base, actions=actions, reply_list=reply_list, count=count, out=out,
+                 out_offsets=out_offsets, ip_ids=ip_ids)
+    _byte_array("actions", actions, n, d)
+    _engine_tensor(engine, d)
+    if not out.is_contiguous() or out.element_size() != 1:
+        raise ValueError("out must be a contiguous 1-byte tensor (the replies are written into it)")
+    m = out_offsets.numel()
+    if out_offsets.element_size() != 8 or out_offsets.is_floating_point() \
+            or not out_offsets.is_contiguous() or m > 0xFFFFFFFF:
+        raise ValueError("out_offsets must be contiguous 8-byte integers, at most 2^32 - 1")
+    if not 0 <= int(slot_bytes) <= 0xFFFF:
+        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
+    if reply_list.element_size() != 4 or not reply_list.is_contiguous() \
+            or reply_list.numel() < min(m, n):
+        raise ValueError("reply_list must be a contiguous 4-byte tensor of >= min(m, n) entries")
+    if count.element_size() != 8 or count.numel() < 1:
+        raise ValueError("count must be the 8-byte count of rx_reply_plan")
+    if ip_ids is not None:
+        _byte_array("ip_ids", ip_ids, m, d, 2)
+    if check and m:
+        so = out_offsets.view(torch.int64)
+        if bool((so < 0).any()) or int(so.max()) + int(slot_bytes) > _nbytes(out):
+            raise ValueError("a reply slot [off, off + slot_bytes) runs past out")
+        ob, oe = out.data_ptr(), out.data_ptr() + _nbytes(out)
+        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
+            raise ValueError("out overlaps base: RX frames and reply slots must not overlap")
+    out_lens = torch.empty(m, dtype=torch.uint16, device=d)
+    built = torch.zeros(1, dtype=torch.int64, device=d)
+    with _on_device(d):
+        _check("wc_rx_reply_build", _lib.active().wc_rx_reply_build(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(actions),
+            reply_list.data_ptr(), count.data_ptr(), engine.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr() if m else None, m, int(slot_bytes),
+            ip_ids.data_ptr() if ip_ids is not None and m else None,
+            out_lens.data_ptr() if m else None, built.data_ptr(), _stream_ptr(stream, d)))
+    return out_lens, built
+
+
+# --------------------------------------------------------------------------
 # TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
 
 # enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)

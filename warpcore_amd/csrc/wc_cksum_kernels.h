@@ -205,6 +205,31 @@ hipError_t launch_rx_demux(const void *base, const uint64_t *offs, const void *r
                            const void *table, uint32_t ns, uint8_t *sock, uint32_t *list,
                            uint64_t *start, void *scratch, hipStream_t st);
 
+// RX replies (wc_k_rxreply.hip) behind an RX verdict / deliver (and demux)
+// launch over the same frames.  Plan: action[i] = the enum wc_rx_reply_action
+// code of frame i by the chain of wc_rx_reply.h over verdict[i], sock[i]
+// (optional) and the engine table `eng` (struct wc_rx_engine, device memory,
+// 4-byte aligned); reply_len[i] = the reply's frame length for a reply action,
+// else 0.  One launch, no atomic.  1 <= n <= 2^32, slot_bytes <= 65535.
+hipError_t launch_rx_reply_plan(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                uint64_t n, const uint8_t *verdict, const uint8_t *sock,
+                                const void *eng, uint32_t slot_bytes, uint8_t *action,
+                                uint16_t *reply_len, bool nt, hipStream_t st);
+// Build: reply j < MIN(*count, m) answers frame list[j] and is written at
+// out_base + out_off[j] (at most slot_bytes bytes), out_len[j] its length; 0,
+// and the slot untouched, for every other j < m and wherever the lengths
+// derived again from the frame, the list index or the action byte do not
+// allow a reply.  *built (zeroed by the caller on `st`) receives the number of
+// non-zero lengths.  One launch of at most as many workgroups as the device's
+// `cus` compute units hold at once (0: no cap), each striding over the replies;
+// m >= 1.
+hipError_t launch_rx_reply_build(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                 uint64_t n, const uint8_t *action, const uint32_t *list,
+                                 const uint64_t *count, const void *eng, void *out_base,
+                                 const uint64_t *out_off, uint32_t m, uint32_t slot_bytes,
+                                 const uint16_t *ip_id, uint16_t *out_len, uint64_t *built,
+                                 int cus, hipStream_t st);
+
 // TX seal of Ethernet frames [base + offs[i], + flens[i]) (wc_k_tx.hip): both
 // checksums computed with their fields taken as 0 and stored raw into the
 // frame, status[i] its enum wc_tx_status code; out_ip / out_udp (optional)

@@ -1,0 +1,377 @@
+// wc_k_rxreply.hip -- the RX reply kernels on gfx950: what the reference's RX
+// path does with a frame beyond delivering it (eth_rx's MAC filter, ip4_rx /
+// ip6_rx's address filter, icmp4_rx / icmp6_rx's checksum verdict, the echo
+// replies and the port / protocol unreachables of udp_rx and ip4_rx), decided
+// and written on the device from the frame bytes and the engine table (struct
+// wc_rx_engine: MAC, MTU, address list).  DESIGN.md section 4.9.  The chain,
+// the reply lengths, the header bytes and the data copy are wc_rx_reply.h's;
+// the frame of the plan kernel (one wave per tile of 64 frames, lane l = frame
+// l, one-shot grid, XCD blocking, the next tile's metadata prefetched) and the
+// gathered stream are the RX verdict's (wc_k_rx.hip, wc_rx_hdr.h).
+//
+// k_rx_reply_plan, per tile:
+//   1. rx_load's five chunks (frame bytes 0..64 at least, each chunk loaded
+//      only if it overlaps the frame) give the Ethernet destination, the
+//      header view (rx_hdr: EtherType, IHL of any value, lengths, protocol /
+//      next header), both IP addresses and the ICMPv6 type byte; no header sum
+//      is taken -- the verdict byte of the RX verdict launch in front has
+//      decided it, and the chain does not decide it again;
+//   2. the engine table is read wave-uniformly (scalar loads of at most 844
+//      bytes, hot in the scalar cache) for the MAC and address filters;
+//   3. the ICMP messages of the lanes that need a sum go through the gathered
+//      stream: [ip + hl, + icmp_len) as plain ip_cksum sums (seg_tile,
+//      WC_KIND_IP: no lane it cannot take), then the ICMPv6 packets [ip, ip +
+//      40 + icmp_len) as payload_cksum (frame_payload_cksum with its per-lane
+//      redo).  Frames that need no sum stream nothing: a tile of UDP frames is
+//      one header round and two stores per lane.
+// No atomic, no wait between workgroups, the same input gives the same output.
+//
+// k_rx_reply_build: one wave per reply at a time (replies are a minority
+// class, and an MTU echo is two 1-KiB steps of the wave), eight waves per
+// workgroup.  The wave reads *count and its list entries itself (one and two
+// replies ahead of the one it builds), derives every length and bound again
+// (rr::reply_of: a stale action byte gives length 0, never an access outside
+// the frame or the slot), then
+//   1. its lanes walk the aligned 16-byte chunks that lie wholly inside the
+//      reply's data region; each is assembled from the two aligned source
+//      chunks that overlap it (source and destination have unrelated byte
+//      phases), stored, and summed as written (rr::copy_chunk); the at most
+//      eight dwords in front of and behind them go the same way one dword per
+//      lane (rr::copy_dword);
+//   2. the sum is reduced across the wave, and lane 0 stores the 42 or 62
+//      header bytes with both checksums (rr::headers, txb::store_headers).
+// Stores are plain vector stores: aligned chunks and dwords inside the reply,
+// byte / 2-byte stores at the two ends of the headers and of the data, so a
+// neighbouring slot that shares a dword, a 16-byte chunk or a cache line keeps
+// every byte of its own (store_raw16's argument in wc_k_tx.hip carries over);
+// headers and data are disjoint byte ranges, so their stores need no order.
+// Reads are aligned chunks and dwords that overlap the request's copied range
+// or header fields, all inside the aligned 16-byte chunks that overlap the
+// frame.
+//
+// No 32-bit sum wraps.  The plan's streams: as the RX verdict's (wc_seg.h); an
+// ICMP message's own sum is at most 32768 words below 2^16.  The build: a
+// reply's data is at most 65535 bytes, so the wave's total of copy_dword's
+// shares is at most 32768 * 0xFFFF < 2^31; the header sums: see rr::headers.
+// The only atomic is the built count's, one per workgroup with a built reply
+// (as many workgroups as the device holds at once).
+// Roofline: HBM -- the ICMP bytes once in the plan, once more (L2-warm behind
+// the plan) in the build, the replies written once.
+#include "wc_rx_hdr.h"
+#include "wc_rx_reply.h"
+
+namespace wc {
+namespace {
+
+typedef uint32_t __attribute__((address_space(1))) *gst32_ptr;
+typedef uint16_t __attribute__((address_space(1))) *gst16_ptr;
+typedef uint8_t __attribute__((address_space(1))) *gst8_ptr;
+typedef const uint32_t __attribute__((address_space(1))) *gld32_ptr;
+typedef u32x4 __attribute__((address_space(1))) *gst128_ptr;
+
+struct ReplyMem { // rr::copy_dword's and txb::store_headers' accesses: global memory
+    __device__ __forceinline__ uint32_t ld32(uint64_t a) const { return *(gld32_ptr)(uintptr_t)a; }
+    __device__ __forceinline__ rr::Quad ld128(uint64_t a) const
+    {
+        const u32x4 v = load_chunk<false>(a);
+        return rr::Quad{v.x, v.y, v.z, v.w};
+    }
+    __device__ __forceinline__ void st128(uint64_t a, const rr::Quad &q) const
+    {
+        *(gst128_ptr)(uintptr_t)a = u32x4{q.x, q.y, q.z, q.w};
+    }
+    __device__ __forceinline__ void st32(uint64_t a, uint32_t v) const
+    {
+        *(gst32_ptr)(uintptr_t)a = v;
+    }
+    __device__ __forceinline__ void st16(uint64_t a, uint32_t v) const
+    {
+        *(gst16_ptr)(uintptr_t)a = (uint16_t)v;
+    }
+    __device__ __forceinline__ void st8(uint64_t a, uint32_t v) const
+    {
+        *(gst8_ptr)(uintptr_t)a = (uint8_t)v;
+    }
+};
+
+__device__ __forceinline__ uint32_t be16(uint32_t x) // a stored 16-bit field, host order
+{
+    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
+}
+
+constexpr int kRrSpan = 15; // XCD super-blocks of 2^15 tiles, as the RX verdict's
+
+// One-wave workgroups and 4 waves per SIMD, as k_rx_verdict.
+template <bool NT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
+k_rx_reply_plan(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
+                const uint16_t *__restrict__ flens, uint64_t n,
+                const uint8_t *__restrict__ verdict, const uint8_t *__restrict__ sock,
+                const uint32_t *__restrict__ eng, uint32_t slot_bytes,
+                uint8_t *__restrict__ action, uint16_t *__restrict__ reply_len)
+{
+    __shared__ FrameLds L;
+    using Src = GathSrc<kFrameUns, NT, false>;
+
+    const int lane = threadIdx.x & 63;
+    seg_init_masks(L.pm, lane); // read after the first row group's wave_order
+    const uint64_t ntiles = (n + 63) / 64;
+    const uint64_t nwaves = gridDim.x;
+    uint64_t tile = xcd_block(kRrSpan << 8);
+    const uint64_t zero = (uint64_t)(uintptr_t)&kZeroChunk;
+    const uint32_t mtu = rr::eng_mtu(eng);
+
+    uint64_t off_n;
+    uint32_t flen_n;
+    meta_load(offs, flens, tile * 64 + lane, n, off_n, flen_n);
+
+    for (; tile < ntiles; tile += nwaves) {
+        const uint64_t p = tile * 64 + lane;
+        const bool valid = p < n;
+        const uint64_t fa = (uint64_t)base + off_n;
+        const uint32_t flen = flen_n;
+        meta_load(offs, flens, (tile + nwaves) * 64 + lane, n, off_n, flen_n);
+        const uint64_t pc = valid ? p : 0;
+        const uint32_t vd = verdict[pc];
+        const uint32_t sk = sock ? sock[pc] : 0u;
+
+        // Frame bytes 0..55 as fourteen dwords: three 20-byte windows rotated
+        // out of the five chunks (frame_hdr's way).
+        u32x4 c[5];
+        rx_load(fa, flen, valid, zero, c);
+        const uint32_t sf = (uint32_t)(fa & 15u);
+        const u32x4 z4 = {0u, 0u, 0u, 0u};
+        uint32_t A[5], B[5], C[4]; // frame bytes 0..19, 20..39, 40..55
+        win_rot(c[0], c[1], c[2], sf, A);
+        const uint32_t o1 = sf + 20u, o2 = sf + 40u;
+        const bool j1 = o1 >= 32u, j2 = o2 >= 48u;
+        win_rot(j1 ? c[2] : c[1], j1 ? c[3] : c[2], j1 ? c[4] : c[3], o1 & 15u, B);
+        win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, C);
+
+        const RxHdr x = rx_hdr(A[3], A[4], B[0], flen);
+        rr::Frame f;
+        f.verdict = valid ? vd : 0xFFu; // (past the batch: NONE, no sum, no store)
+        f.flen = flen;
+        f.unbound = sock != nullptr && sk == rr::kSockUnbound;
+        f.v4 = x.v4;
+        f.hl = x.hl;
+        f.proto = x.proto;
+        f.ip_len = x.v4 ? be16(A[4]) : be16(A[4] >> 16); // bytes 16..17 / 18..19
+        // IPv4 src @26, dst @30; IPv6 src @22..37, dst @38..53
+        uint32_t src[4], dst[4];
+        src[0] = x.v4 ? (B[1] >> 16) | (B[2] << 16) : (B[0] >> 16) | (B[1] << 16);
+        src[1] = (B[1] >> 16) | (B[2] << 16);
+        src[2] = (B[2] >> 16) | (B[3] << 16);
+        src[3] = (B[3] >> 16) | (B[4] << 16);
+        dst[0] = x.v4 ? (B[2] >> 16) | (B[3] << 16) : (B[4] >> 16) | (C[0] << 16);
+        dst[1] = (C[0] >> 16) | (C[1] << 16);
+        dst[2] = (C[1] >> 16) | (C[2] << 16);
+        dst[3] = (C[2] >> 16) | (C[3] << 16);
+        f.mac_ok = rr::mac_ok(eng, A[0], A[1]);
+        const rr::Match am = rr::addr_match(eng, x.v4, dst, src);
+        f.dst_ok = am.dst;
+        f.src_ok = am.src;
+
+        uint32_t sum_len;
+        rr::Reply r = rr::chain_head(f, mtu, slot_bytes, sum_len);
+        const bool need4 = r.action == rr::kSum4 && sum_len != 0u; // (no byte: 0xFFFF)
+        const bool need6 = r.action == rr::kSum6;
+        const uint64_t ip = fa + 14u;
+        // The ICMP type byte at ip + hl (inside the frame wherever a byte is
+        // summed), issued ahead of the stream; ICMPv6's is frame byte 54.
+        const uint64_t ta = ip + x.hl;
+        const u32x4 tc = load_chunk<false>(need4 ? ta & ~15ull : zero);
+        uint32_t ck = 0xFFFFu;
+        if (__ballot(need4)) {
+            const uint32_t len = need4 ? sum_len : 0u;
+            const FlatTile ft = flat_tile_setup<kFrameUns, 1>(L.f, lane, ta, len, len, need4, 0u);
+            bool done = true;
+            uint16_t rh = 0;
+            const uint32_t s4 = seg_tile<kFrameUns, WC_KIND_IP, NT, false, Src, false>(
+                L.f.pre, L.stage, L.pm, lane, ta, 16ull * ft.cp + (ta & 15u), len, need4, ft.total,
+                Src{&L.f, ft}, zero, done, rh);
+            if (need4)
+                ck = s4;
+            wave_order(); // the tables are rewritten by the next stream
+        }
+        const uint32_t s6 = frame_payload_cksum<NT>(L, lane, ip, need6 ? sum_len : 0u, need6, zero);
+        if (need6)
+            ck = s6;
+        if (r.action == rr::kSum4 || r.action == rr::kSum6) {
+            const uint32_t type = r.action == rr::kSum4 ? pick_byte(tc, (int)(ta & 15u))
+                                                        : (C[3] >> 16) & 0xFFu;
+            r = rr::chain_tail(r.action, f, ck, type, mtu, slot_bytes);
+        }
+        if (valid) {
+            action[p] = (uint8_t)r.action;
+            reply_len[p] = (uint16_t)r.len;
+        }
+    }
+}
+
+// kBuildWaves waves per workgroup, one reply each at a time; the grid is capped
+// at what the device holds at once (launch_rx_reply_build) and strides over m,
+// so the built count costs one atomic per resident workgroup: one per four
+// replies serialised a flood of 2^18 echoes at 12 ns apiece, 810 us
+// (profiles/ab_rxreply_build.log).
+constexpr uint32_t kBuildWaves = 8;
+
+// What the build reads about reply j in front of the frame itself: its list
+// entry's action, frame offset and length, its slot and ip->id.  `idx` is the
+// list entry, ~0 past MIN(*count, m); live: the entry names a frame.
+struct BuildMeta {
+    uint64_t off, ooff;
+    uint32_t act, flen, ipid;
+    bool live;
+};
+
+__device__ __forceinline__ BuildMeta build_meta(uint32_t idx, uint64_t j, uint32_t m, uint64_t n,
+                                                const uint8_t *__restrict__ action,
+                                                const uint64_t *__restrict__ offs,
+                                                const uint16_t *__restrict__ flens,
+                                                const uint64_t *__restrict__ out_off,
+                                                const uint16_t *__restrict__ ip_id)
+{
+    BuildMeta t{0u, 0u, 0u, 0u, 0u, false};
+    if (j < m) {
+        t.ooff = out_off[j];
+        t.ipid = ip_id ? (uint32_t)ip_id[j] : 0u;
+        if (idx < n) {
+            t.act = action[idx];
+            t.off = offs[idx];
+            t.flen = flens[idx];
+            t.live = true;
+        }
+    }
+    return t;
+}
+
+__global__ void __launch_bounds__(64 * kBuildWaves)
+k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
+                 const uint16_t *__restrict__ flens, uint64_t n,
+                 const uint8_t *__restrict__ action, const uint32_t *__restrict__ list,
+                 const unsigned long long *__restrict__ count, const uint32_t *__restrict__ eng,
+                 uint8_t *out_base, const uint64_t *__restrict__ out_off, uint32_t m,
+                 uint32_t slot_bytes, const uint16_t *__restrict__ ip_id,
+                 uint16_t *__restrict__ out_len, unsigned long long *__restrict__ built)
+{
+    __shared__ uint32_t nb[kBuildWaves];
+    const int lane = threadIdx.x & 63;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t cnt = *count;
+    const uint64_t lim = cnt < m ? cnt : (uint64_t)m;
+    const uint32_t mtu = rr::eng_mtu(eng);
+    const ReplyMem mem{};
+    uint32_t nbuilt = 0; // wave-uniform
+
+    // A wave's replies are j, j + S, ...; each costs two dependent load rounds
+    // in front of its stores (the frame's length fields; then its addresses and
+    // data), because the two rounds in front of those -- the list entry, then
+    // what it names -- are issued one and two replies ahead, beside the loads
+    // of the reply being built.
+    const uint64_t S = (uint64_t)gridDim.x * kBuildWaves;
+    uint64_t j = (uint64_t)blockIdx.x * kBuildWaves + w;
+    BuildMeta cur = build_meta(j < lim ? list[j] : 0xFFFFFFFFu, j, m, n, action, offs, flens,
+                               out_off, ip_id);
+    uint32_t idx_n = j + S < lim ? list[j + S] : 0xFFFFFFFFu;
+    for (; j < m; j += S) {
+        const BuildMeta nxt = build_meta(idx_n, j + S, m, n, action, offs, flens, out_off, ip_id);
+        idx_n = j + 2 * S < lim ? list[j + 2 * S] : 0xFFFFFFFFu;
+        uint32_t len = 0;
+        if (cur.live && rr::is_reply(cur.act)) { // (wave-uniform branches throughout)
+            const uint32_t act = cur.act, flen = cur.flen;
+            const uint64_t fa = (uint64_t)(uintptr_t)base + cur.off;
+            const uint64_t fend = fa + flen;
+            // vhl, tos, ip->len (IPv4) and ip6->len: frame bytes 14..17, 18..19
+            const uint32_t g0 = rr::frame_dword(mem, fa, fend, 14u);
+            const uint32_t g1 = rr::frame_dword(mem, fa, fend, 18u);
+            const bool v4 = rr::reply_v4(act);
+            const uint32_t hl = v4 ? ((g0 & 15u) * 4u) : 40u;
+            const uint32_t ip_len = v4 ? be16(g0 >> 16) : be16(g1);
+            const rr::Reply r = rr::reply_of(act, hl, ip_len, flen, mtu, slot_bytes);
+            if (rr::is_reply(r.action)) {
+                const rr::Req q = rr::request_of(mem, fa, fend, act, hl);
+                const uint64_t da = (uint64_t)(uintptr_t)out_base + cur.ooff;
+                const uint64_t dd = da + (v4 ? 42u : 62u), sa = fa + r.s0;
+                const uint32_t nd = rr::copy_dwords(dd, r.dlen);
+                const rr::Chunks ch = rr::copy_chunks(dd, r.dlen);
+                uint32_t acc = 0;
+                for (uint32_t c = ch.c0 + (uint32_t)lane; c < ch.c1; c += 64u)
+                    acc += rr::copy_chunk(mem, sa, dd, c);
+                // the dwords in front of and behind the whole chunks: at most 4 + 4
+                const uint32_t i = (uint32_t)lane < ch.i0 ? (uint32_t)lane
+                                                          : ch.i1 + ((uint32_t)lane - ch.i0);
+                if (i < nd)
+                    acc += rr::copy_dword(mem, sa, dd, r.dlen, i);
+                const uint32_t data = rr::fold16(group_sum<64>(acc));
+                uint32_t h[16];
+                rr::headers(r, q, eng, cur.ipid, data, h);
+                if (lane == 0)
+                    txb::store_headers(mem, da, v4, h);
+                len = r.len;
+            }
+        }
+        if (lane == 0)
+            out_len[j] = (uint16_t)len;
+        nbuilt += len != 0u;
+        cur = nxt;
+    }
+    if (lane == 0)
+        nb[w] = nbuilt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (uint32_t k = 0; k < kBuildWaves; ++k)
+            s += nb[k];
+        if (s)
+            atomicAdd(built, (unsigned long long)s);
+    }
+}
+
+} // namespace
+
+hipError_t launch_rx_reply_plan(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                uint64_t n, const uint8_t *verdict, const uint8_t *sock,
+                                const void *eng, uint32_t slot_bytes, uint8_t *action,
+                                uint16_t *reply_len, bool nt, hipStream_t st)
+{
+    const uint64_t tiles = (n + 63) / 64;
+    const int grid = (int)std::min<uint64_t>(kMaxGridBlocks, std::max<uint64_t>(1, tiles));
+    if (nt)
+        hipLaunchKernelGGL((k_rx_reply_plan<true>), dim3(grid), dim3(64), 0, st,
+                           (const uint8_t *)base, offs, flens, n, verdict, sock,
+                           (const uint32_t *)eng, slot_bytes, action, reply_len);
+    else
+        hipLaunchKernelGGL((k_rx_reply_plan<false>), dim3(grid), dim3(64), 0, st,
+                           (const uint8_t *)base, offs, flens, n, verdict, sock,
+                           (const uint32_t *)eng, slot_bytes, action, reply_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_rx_reply_build(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                 uint64_t n, const uint8_t *action, const uint32_t *list,
+                                 const uint64_t *count, const void *eng, void *out_base,
+                                 const uint64_t *out_off, uint32_t m, uint32_t slot_bytes,
+                                 const uint16_t *ip_id, uint16_t *out_len, uint64_t *built,
+                                 int cus, hipStream_t st)
+{
+    // The grid: what the device holds at once (a workgroup that had to wait for
+    // a slot would start its share of the replies when the others are done).
+    static const int per_cu = [] {
+        int k = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, k_rx_reply_build, 64 * kBuildWaves, 0) !=
+                hipSuccess || k < 1)
+            k = 1;
+        return k;
+    }();
+    const uint64_t blocks = ((uint64_t)m + kBuildWaves - 1) / kBuildWaves;
+    const uint64_t cap = cus > 0 ? (uint64_t)cus * per_cu : kMaxGridBlocks;
+    const int grid = (int)std::min<uint64_t>(cap, std::max<uint64_t>(1, blocks));
+    hipLaunchKernelGGL(k_rx_reply_build, dim3(grid), dim3(64 * kBuildWaves), 0, st, (const uint8_t *)base, offs,
+                       flens, n, action, list, (const unsigned long long *)count,
+                       (const uint32_t *)eng, (uint8_t *)out_base, out_off, m, slot_bytes, ip_id,
+                       out_len, (unsigned long long *)built);
+    return hipGetLastError();
+}
+
+} // namespace wc
