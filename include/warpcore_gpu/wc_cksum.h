@@ -603,6 +603,128 @@ int wc_rx_reply_build(const void *d_base, const uint64_t *d_off, const uint16_t 
                       const uint16_t *d_ip_id /* optional, m entries */,
                       uint16_t *d_out_len, uint64_t *d_built, void *stream);
 
+/* --- RX neighbours: ARP / ND replies and cache updates --------------------- */
+
+/* What the reference does with the frames wc_rx_reply_plan marks WC_RR_HOST:
+ * arp_rx (arp.c:157-198) with its is-at reply (arp_is_at, arp.c:65-100), and
+ * the neighbour solicitation / advertisement branches of icmp6_rx
+ * (icmp6.c:270-322) with the advertisement icmp6_tx writes (icmp6.c:168-193,
+ * 221-228).  All of it is a function of the frame bytes and the engine table;
+ * the host applies the (address, MAC) records to its cache in order
+ * (neighbor_update) and posts the built frames.  The cache itself, the who_has
+ * loop and its solicitations stay the host's. */
+enum wc_rx_neigh_action {        /* uint8, all < 32 so wc_rx_select masks apply */
+    WC_RN_NONE = 0,              /* nothing to do */
+    WC_RN_MALFORMED = 4,         /* a byte the reference would read lies past the frame */
+    WC_RN_UPDATE4 = 8,           /* ARP: cache update only */
+    WC_RN_ARP_IS_AT = 9,         /* ARP request for us: update plus a 42-byte is-at */
+    WC_RN_NADV = 10,             /* solicitation for us: update plus an 86-byte advertisement */
+    WC_RN_UPDATE6 = 11,          /* advertisement received: update only */
+};
+#define WC_RN_MASK_REPLY  (0x600u)
+#define WC_RN_MASK_UPDATE (0xF00u)
+
+struct wc_neigh_update {         /* 24 bytes: what neighbor_update receives */
+    uint8_t af;                  /* 4 or 6; 0: an empty record */
+    uint8_t action;              /* the enum wc_rx_neigh_action code it came from */
+    uint8_t mac[6];
+    uint8_t addr[16];            /* af 4: bytes 0..3, the rest 0 */
+};
+
+/* Behind a wc_rx_reply_plan of the same frames on the same stream: it reads
+ * its d_action and does not decide again what the calls in front decided (the
+ * MAC filter, the IPv6 address filter, the ICMPv6 checksum).  d_nact[i] = frame
+ * i's enum wc_rx_neigh_action code.  With d_rlist / d_rcount:
+ * wc_rx_select(d_nact, n, WC_RN_MASK_REPLY, ...); with d_ulist / d_ucount: the
+ * same with WC_RN_MASK_UPDATE; both on the same stream, one after the other
+ * through the one d_scratch of wc_rx_select_scratch(n) bytes.  For each pair
+ * both pointers are given or neither: checked first, for every n.
+ *
+ * The chain; the first hit names the code.  Frame bytes are numbered from the
+ * Ethernet header, flen is the frame length.
+ *   1. d_action[i] != WC_RR_HOST (or flen < 14: no EtherType):      NONE.
+ *   2. Bytes 12..13 are 08 06 (eth.c:80-83):
+ *      a. no af-4 entry in the table (w->have_ip4):                  NONE.
+ *      b. flen < 42:                                                 MALFORMED.
+ *      c. bytes 14..15 are not 00 01, or byte 18 is not 6 (arp.c:161): NONE.
+ *      d. bytes 16..17 are not 08 00, or byte 19 is not 4 (arp.c:167): NONE.
+ *      e. bytes 20..21: 00 01 -- ARP_IS_AT if bytes 38..41 equal the addr of
+ *         an af-4 entry (is_my_ip4 without the broadcast match: bcast and
+ *         255.255.255.255 do not match), else UPDATE4 (the reference updates
+ *         the cache for requests that are not for us too, arp.c:181-183, 196);
+ *         00 02 -- UPDATE4; anything else -- NONE.
+ *   3. Bytes 12..13 are 86 dd:
+ *      a. flen < 55, or byte 20 is not 58, or byte 54 is neither 135 nor 136
+ *         (a stale action byte):                                     NONE.
+ *      b. flen < 78 (the 16 target bytes 62..77):                    MALFORMED.
+ *      c. byte 54 is 136:                                            UPDATE6.
+ *      d. byte 54 is 135: NADV if bytes 62..77 equal the addr of an af-6
+ *         entry (is_my_ip6 without snma / bcast; af-6 entries only, the reply
+ *         plan's deliberate difference), else NONE (icmp6.c:312-321: no
+ *         update either).
+ *   4. Any other EtherType:                                          NONE.
+ * n = 0 is WC_OK and writes 0 to whichever counts are given.  WC_EINVAL: a
+ * list without its count or a count without its list, n > 2^32, a NULL d_base
+ * / d_off / d_frame_len / d_action / d_eng / d_nact, d_eng not 4-byte aligned,
+ * a list without a 4-byte-aligned d_scratch.  Asynchronous on `stream`: one
+ * launch and three per list; no library lock, no atomic, and the same input
+ * gives the same output.  No byte outside a frame is read (reads are the
+ * aligned 16-byte chunks that overlap it), and no frame byte at all of a frame
+ * whose action is not WC_RR_HOST. */
+int wc_rx_neigh_plan(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                     const uint8_t *d_action, const struct wc_rx_engine *d_eng, uint8_t *d_nact,
+                     uint32_t *d_rlist, uint64_t *d_rcount, uint32_t *d_ulist, uint64_t *d_ucount,
+                     void *d_scratch, void *stream);
+
+/* For j < MIN(*d_count, m), d_upd[j] is the record of frame d_list[j] (the
+ * plan's d_ulist / d_ucount; *d_count is read on the device).  The records
+ * come out in ring order, so applying them in order leaves the cache as the
+ * reference would.
+ *   UPDATE4, ARP_IS_AT: af 4, addr = bytes 28..31 (spa), mac = bytes 22..27 (sha).
+ *   UPDATE6: af 6, addr = bytes 62..77 (the target); NADV: af 6, addr = the IPv6
+ *     source, bytes 22..37 (icmp6.c:316-318).  mac, for both (icmp6.c:272-282,
+ *     295-304): with data_len = MIN(ip6 payload length, flen - 62), bytes
+ *     80..85 if data_len >= 24 and bytes 78..79 are 01 01, else bytes 6..11 (the
+ *     reference tests option type 1 on a received advertisement too).
+ * The record is all zero where the index is >= n, the code is no update code
+ * or the frame is shorter than 42 / 78, and for MIN(*d_count, m) <= j < m.
+ * m = 0 is WC_OK and looks at no pointer; n = 0 writes m zero records.
+ * WC_EINVAL: n > 2^32, with m > 0 a NULL or not 4-byte-aligned d_upd, with m >
+ * 0 and n > 0 any other NULL pointer.  One launch, no atomic; no byte outside a
+ * frame is read (reads are aligned dwords that overlap it). */
+int wc_rx_neigh_updates(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                        const uint8_t *d_nact, const uint32_t *d_list, const uint64_t *d_count,
+                        uint32_t m, struct wc_neigh_update *d_upd, void *stream);
+
+/* The contract of wc_rx_reply_build for the plan's d_rlist / d_rcount: reply
+ * j < MIN(*d_count, m) answers frame d_list[j], is written at d_out_base +
+ * d_out_off[j] and d_out_len[j] is its length; *d_built is written, not
+ * accumulated.  d_out_len[j] is 0 and the slot untouched where the index is >=
+ * n, the code is no reply code, the frame is shorter than 42 / 78, slot_bytes
+ * is below 42 / 86, or j is at or past the count.  Nothing outside [slot, slot
+ * + length) is written; all stores are plain vector stores.
+ *   ARP_IS_AT, 42 bytes (arp.c:78-96): dst = request bytes 22..27 (its sha, not
+ *     its Ethernet source), src = mac, 08 06; 00 01 08 00 06 04 00 02; sha =
+ *     mac, spa = request bytes 38..41, tha = request bytes 22..27, tpa =
+ *     request bytes 28..31.
+ *   NADV, 86 bytes: dst = request bytes 6..11, src = mac, 86 dd; 60 00 00 00
+ *     (written whole, as the existing replies), 00 20, 3a, ff, src = entry 0's
+ *     address, dst = request bytes 22..37; 88 00, checksum, 60 00 00 00,
+ *     request bytes 62..77, 02 01, mac.  Checksum: payload_cksum(ip, 72) with
+ *     the field taken as 0, stored raw.  A reference quirk is kept: icmp6_tx's
+ *     source-link-address test reads the ICMPv6 type and code bytes
+ *     (icmp6.c:163, 173-175), never 01 01 for a solicitation, so the Ethernet
+ *     destination is always the request's source MAC.
+ * m = 0 is WC_OK, writes *d_built = 0 and looks at no other pointer; n = 0
+ * writes that and m zero lengths.  WC_EINVAL: as wc_rx_reply_build.  The only
+ * atomic is the built count's, one per workgroup of a grid no larger than the
+ * device holds at once. */
+int wc_rx_neigh_build(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                      const uint8_t *d_nact, const uint32_t *d_list, const uint64_t *d_count,
+                      const struct wc_rx_engine *d_eng,
+                      void *d_out_base, const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
+                      uint16_t *d_out_len, uint64_t *d_built, void *stream);
+
 /* --- host-memory batch (end-to-end: pinned H2D, kernel, D2H) ------------- */
 
 /* Same as wc_cksum_ragged, but every buffer is host memory: packet i is

@@ -51,6 +51,10 @@ SIGNATURES = {
                                 _vp]),
     "wc_rx_reply_build": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
                                  _vp, _vp, _vp, _vp]),
+    "wc_rx_neigh_plan": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wc_rx_neigh_updates": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "wc_rx_neigh_build": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
+                                 _vp, _vp, _vp]),
     "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "wc_tx_socks_check": (_int, [_vp, _u32]),

@@ -805,6 +805,143 @@ def rx_reply_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.
 
 
 # --------------------------------------------------------------------------
+# RX neighbours (arp_rx / arp_is_at and the NSOL / NADV branches of icmp6_rx /
+# icmp6_tx: replies and neighbor_update records).
+
+# enum wc_rx_neigh_action
+RN_NONE, RN_MALFORMED = 0, 4
+RN_UPDATE4, RN_ARP_IS_AT, RN_NADV, RN_UPDATE6 = range(8, 12)
+RN_MASK_REPLY, RN_MASK_UPDATE = 0x600, 0xF00
+RN_NAMES = {RN_NONE: "none", RN_MALFORMED: "malformed", RN_UPDATE4: "update4",
+            RN_ARP_IS_AT: "arp_is_at", RN_NADV: "nadv", RN_UPDATE6: "update6"}
+# struct wc_neigh_update (include/warpcore_gpu/wc_cksum.h): 24 bytes
+NEIGH_UPDATE = np.dtype([("af", "u1"), ("action", "u1"), ("mac", "u1", 6), ("addr", "u1", 16)])
+assert NEIGH_UPDATE.itemsize == 24
+
+
+def _list_args(name: str, lst: torch.Tensor, count: torch.Tensor, m: int, n: int, device) -> None:
+    if not isinstance(lst, torch.Tensor) or not isinstance(count, torch.Tensor) \
+            or lst.device != device or count.device != device:
+        raise ValueError(f"{name} and its count must be device tensors on {device}")
+    if lst.element_size() != 4 or not lst.is_contiguous() or lst.numel() < min(m, n):
+        raise ValueError(f"{name} must be a contiguous 4-byte tensor of >= min(m, n) entries")
+    if count.element_size() != 8 or count.numel() < 1:
+        raise ValueError("count must be the 8-byte count of rx_neigh_plan")
+
+
+def rx_neigh_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                  actions: torch.Tensor, engine: torch.Tensor, want_replies: bool = True,
+                  want_updates: bool = True, stream=None, check: bool = True,
+                  scratch: Optional[torch.Tensor] = None):
+    """What the reference does with the frames rx_reply_plan marked RR_HOST
+    (wc_rx_neigh_plan): ARP and ICMPv6 neighbour solicitations / advertisements.
+    ``actions`` are rx_reply_plan's, ``engine`` its RX_ENGINE tensor.  Returns
+    ``(nact uint8 RN_*, reply_list, reply_count, update_list, update_count)``:
+    the lists / counts as rx_select gives them for ``RN_MASK_REPLY`` and
+    ``RN_MASK_UPDATE`` (None, None where not wanted).  Asynchronous; the
+    scratch is allocated here unless given."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    d = base.device
+    _byte_array("actions", actions, n, d)
+    _engine_tensor(engine, d)
+    nact = torch.empty(n, dtype=torch.uint8, device=d)
+    rl = rc = ul = uc = None
+    if want_replies:
+        rl, _ = _index_list(None, n, d)
+        rc = torch.zeros(1, dtype=torch.int64, device=d)
+    if want_updates:
+        ul, _ = _index_list(None, n, d)
+        uc = torch.zeros(1, dtype=torch.int64, device=d)
+    if want_replies or want_updates:
+        if scratch is None:
+            scratch = _scratch(rx_select_scratch(n), d)
+        elif _nbytes(scratch) < rx_select_scratch(n) or scratch.device != d:
+            raise ValueError(f"scratch must hold rx_select_scratch(n) bytes on {d}")
+    else:
+        scratch = None
+    with _on_device(d):
+        _check("wc_rx_neigh_plan", _lib.active().wc_rx_neigh_plan(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(actions),
+            engine.data_ptr(), nact.data_ptr() if n else None,
+            rl.data_ptr() if want_replies else None, rc.data_ptr() if want_replies else None,
+            ul.data_ptr() if want_updates else None, uc.data_ptr() if want_updates else None,
+            scratch.data_ptr() if scratch is not None else None, _stream_ptr(stream, d)))
+    return (nact, rl[:n] if want_replies else None, rc, ul[:n] if want_updates else None, uc)
+
+
+def rx_neigh_updates(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                     nact: torch.Tensor, update_list: torch.Tensor, count: torch.Tensor, m: int,
+                     stream=None, check: bool = True) -> torch.Tensor:
+    """The neighbor_update records of the frames rx_neigh_plan listed
+    (wc_rx_neigh_updates): an ``(m, 24)`` uint8 device tensor, record ``j <
+    min(count, m)`` that of frame ``update_list[j]``, the rest all zero (on the
+    host: ``.cpu().numpy().view(NEIGH_UPDATE)``).  In ring order: apply them in
+    order.  ``count`` is read on the device: no synchronisation."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    m = int(m)
+    if not 0 <= m <= 0xFFFFFFFF:
+        raise ValueError("m is a uint32")
+    d = base.device
+    _byte_array("nact", nact, n, d)
+    _list_args("update_list", update_list, count, m, n, d)
+    upd = torch.empty((m, NEIGH_UPDATE.itemsize), dtype=torch.uint8, device=d)
+    with _on_device(d):
+        _check("wc_rx_neigh_updates", _lib.active().wc_rx_neigh_updates(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(nact),
+            update_list.data_ptr(), count.data_ptr(), m, upd.data_ptr() if m else None,
+            _stream_ptr(stream, d)))
+    return upd
+
+
+def rx_neigh_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+                   nact: torch.Tensor, reply_list: torch.Tensor, count: torch.Tensor,
+                   engine: torch.Tensor, out: torch.Tensor, out_offsets: torch.Tensor,
+                   slot_bytes: int, stream=None, check: bool = True):
+    """Write the is-at and advertisement frames rx_neigh_plan listed
+    (wc_rx_neigh_build), with rx_reply_build's contract: reply ``j < min(count,
+    m)``, ``m = out_offsets.numel()``, answers frame ``reply_list[j]`` at
+    ``out[out_offsets[j]]``.  Returns ``(out_lens uint16 -- 0 where no reply was
+    written --, built)``."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
+    if n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    d = base.device
+    _same_device(base, nact=nact, reply_list=reply_list, count=count, out=out,
+                 out_offsets=out_offsets)
+    _byte_array("nact", nact, n, d)
+    _engine_tensor(engine, d)
+    if not out.is_contiguous() or out.element_size() != 1:
+        raise ValueError("out must be a contiguous 1-byte tensor (the replies are written into it)")
+    m = out_offsets.numel()
+    if out_offsets.element_size() != 8 or out_offsets.is_floating_point() \
+            or not out_offsets.is_contiguous() or m > 0xFFFFFFFF:
+        raise ValueError("out_offsets must be contiguous 8-byte integers, at most 2^32 - 1")
+    if not 0 <= int(slot_bytes) <= 0xFFFF:
+        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
+    _list_args("reply_list", reply_list, count, m, n, d)
+    if check and m:
+        so = out_offsets.view(torch.int64)
+        if bool((so < 0).any()) or int(so.max()) + int(slot_bytes) > _nbytes(out):
+            raise ValueError("a reply slot [off, off + slot_bytes) runs past out")
+        ob, oe = out.data_ptr(), out.data_ptr() + _nbytes(out)
+        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
+            raise ValueError("out overlaps base: RX frames and reply slots must not overlap")
+    out_lens = torch.empty(m, dtype=torch.uint16, device=d)
+    built = torch.zeros(1, dtype=torch.int64, device=d)
+    with _on_device(d):
+        _check("wc_rx_neigh_build", _lib.active().wc_rx_neigh_build(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(nact),
+            reply_list.data_ptr(), count.data_ptr(), engine.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr() if m else None, m, int(slot_bytes),
+            out_lens.data_ptr() if m else None, built.data_ptr(), _stream_ptr(stream, d)))
+    return out_lens, built
+
+
+# --------------------------------------------------------------------------
 # TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
 
 # enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)

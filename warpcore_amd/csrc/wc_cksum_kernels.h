@@ -230,6 +230,29 @@ hipError_t launch_rx_reply_build(const void *base, const uint64_t *offs, const u
                                  const uint16_t *ip_id, uint16_t *out_len, uint64_t *built,
                                  int cus, hipStream_t st);
 
+// RX neighbours (wc_k_rxneigh.hip) behind a reply plan launch over the same
+// frames.  Plan: nact[i] = the enum wc_rx_neigh_action code of frame i by the
+// chain of wc_rx_neigh.h over action[i] (the reply plan's) and the engine table
+// `eng` (4-byte aligned).  One launch, no atomic.  1 <= n <= 2^32.
+hipError_t launch_rx_neigh_plan(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                uint64_t n, const uint8_t *action, const void *eng, uint8_t *nact,
+                                hipStream_t st);
+// Updates: upd[j] (struct wc_neigh_update, 4-byte aligned) = the record of
+// frame list[j] for j < MIN(*count, m), all zero for every other j < m and
+// wherever the index, the code byte or the frame length allow no record.
+// Build: as launch_rx_reply_build, for the is-at and advertisement frames.
+// Each is one launch of at most as many workgroups as the device's `cus`
+// compute units hold at once (0: no cap); m >= 1.
+hipError_t launch_rx_neigh_updates(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                   uint64_t n, const uint8_t *nact, const uint32_t *list,
+                                   const uint64_t *count, uint32_t m, void *upd, int cus,
+                                   hipStream_t st);
+hipError_t launch_rx_neigh_build(const void *base, const uint64_t *offs, const uint16_t *flens,
+                                 uint64_t n, const uint8_t *nact, const uint32_t *list,
+                                 const uint64_t *count, const void *eng, void *out_base,
+                                 const uint64_t *out_off, uint32_t m, uint32_t slot_bytes,
+                                 uint16_t *out_len, uint64_t *built, int cus, hipStream_t st);
+
 // TX seal of Ethernet frames [base + offs[i], + flens[i]) (wc_k_tx.hip): both
 // checksums computed with their fields taken as 0 and stored raw into the
 // frame, status[i] its enum wc_tx_status code; out_ip / out_udp (optional)

@@ -1,0 +1,120 @@
+// wc_rt_rxneigh.cpp -- RX neighbours (wc_rx_neigh_plan, wc_rx_neigh_updates,
+// wc_rx_neigh_build): the plan launch with its two lists (wc_rx_select's three
+// launches each, one after the other through the one scratch), and the one
+// launch each that writes the cache-update records and the reply frames
+// (DESIGN.md section 4.10).
+
+#include "wc_rt.h"
+#include "wc_rx_neigh.h"
+
+using namespace wc::rt;
+namespace rn = wc::rn;
+
+static_assert(sizeof(struct wc_neigh_update) == 24, "the record as six dwords");
+static_assert(WC_RN_NONE == rn::kNone && WC_RN_MALFORMED == rn::kMalformed &&
+                  WC_RN_UPDATE4 == rn::kUpdate4 && WC_RN_ARP_IS_AT == rn::kArpIsAt &&
+                  WC_RN_NADV == rn::kNadv && WC_RN_UPDATE6 == rn::kUpdate6 &&
+                  WC_RN_MASK_REPLY == rn::kMaskReply && WC_RN_MASK_UPDATE == rn::kMaskUpdate &&
+                  WC_RR_HOST == wc::rr::kHost,
+              "header and kernels agree");
+static_assert(rn::kMaskReply == ((1u << rn::kArpIsAt) | (1u << rn::kNadv)) &&
+                  rn::kMaskUpdate == ((1u << rn::kUpdate4) | (1u << rn::kUpdate6) | rn::kMaskReply),
+              "the masks are the codes' bits");
+
+static constexpr uint64_t kRxNeighMax = 1ull << 32; // the lists' indices are uint32
+
+extern "C" {
+
+int wc_rx_neigh_plan(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
+                     uint64_t n, const uint8_t *d_action, const struct wc_rx_engine *d_eng,
+                     uint8_t *d_nact, uint32_t *d_rlist, uint64_t *d_rcount, uint32_t *d_ulist,
+                     uint64_t *d_ucount, void *d_scratch, void *stream)
+{
+    if ((d_rlist != nullptr) != (d_rcount != nullptr) || (d_ulist != nullptr) != (d_ucount != nullptr))
+        return WC_EINVAL;
+    if (n > kRxNeighMax)
+        return WC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { // an empty batch: zero counts (device memory, so on the caller's stream)
+        if (!d_rcount && !d_ucount)
+            return WC_OK;
+        Ready R;
+        if (R.rc)
+            return R.rc;
+        hipError_t e = hipSuccess;
+        if (d_rcount)
+            e = hipMemsetAsync(d_rcount, 0, sizeof(uint64_t), st);
+        if (e == hipSuccess && d_ucount)
+            e = hipMemsetAsync(d_ucount, 0, sizeof(uint64_t), st);
+        return hip_err(e);
+    }
+    if (!d_base || !d_off || !d_frame_len || !d_action || !d_eng || ((uintptr_t)d_eng & 3u) || !d_nact)
+        return WC_EINVAL;
+    if ((d_rlist || d_ulist) && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
+        return WC_EINVAL;
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    hipError_t e = wc::launch_rx_neigh_plan(d_base, d_off, d_frame_len, n, d_action, d_eng, d_nact, st);
+    if (e == hipSuccess && d_rlist)
+        e = wc::launch_rx_select(d_nact, n, WC_RN_MASK_REPLY, d_rlist, d_rcount, d_scratch, st);
+    if (e == hipSuccess && d_ulist)
+        e = wc::launch_rx_select(d_nact, n, WC_RN_MASK_UPDATE, d_ulist, d_ucount, d_scratch, st);
+    return hip_err(e);
+}
+
+int wc_rx_neigh_updates(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
+                        uint64_t n, const uint8_t *d_nact, const uint32_t *d_list,
+                        const uint64_t *d_count, uint32_t m, struct wc_neigh_update *d_upd,
+                        void *stream)
+{
+    if (n > kRxNeighMax)
+        return WC_EINVAL;
+    if (m != 0 && (!d_upd || ((uintptr_t)d_upd & 3u)))
+        return WC_EINVAL;
+    if (m != 0 && n != 0 && (!d_base || !d_off || !d_frame_len || !d_nact || !d_list || !d_count))
+        return WC_EINVAL;
+    if (m == 0)
+        return WC_OK;
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    hipError_t e;
+    if (n == 0) // no frame, no record
+        e = hipMemsetAsync(d_upd, 0, sizeof(struct wc_neigh_update) * (size_t)m, (hipStream_t)stream);
+    else
+        e = wc::launch_rx_neigh_updates(d_base, d_off, d_frame_len, n, d_nact, d_list, d_count, m,
+                                        d_upd, R.D->cus, (hipStream_t)stream);
+    return hip_err(e);
+}
+
+int wc_rx_neigh_build(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
+                      uint64_t n, const uint8_t *d_nact, const uint32_t *d_list,
+                      const uint64_t *d_count, const struct wc_rx_engine *d_eng, void *d_out_base,
+                      const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
+                      uint16_t *d_out_len, uint64_t *d_built, void *stream)
+{
+    if (n > kRxNeighMax || slot_bytes > 65535u || !d_built)
+        return WC_EINVAL;
+    if (m != 0 && !d_out_len)
+        return WC_EINVAL;
+    if (m != 0 && n != 0 &&
+        (!d_base || !d_off || !d_frame_len || !d_nact || !d_list || !d_count || !d_eng ||
+         ((uintptr_t)d_eng & 3u) || !d_out_base || !d_out_off))
+        return WC_EINVAL;
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    // The count of built replies: zeroed here, added to by the launch's
+    // workgroups, as many as the device holds at once.
+    hipError_t e = hipMemsetAsync(d_built, 0, sizeof(uint64_t), (hipStream_t)stream);
+    if (e == hipSuccess && m != 0 && n == 0) // no frame, no reply
+        e = hipMemsetAsync(d_out_len, 0, sizeof(uint16_t) * (size_t)m, (hipStream_t)stream);
+    else if (e == hipSuccess && m != 0)
+        e = wc::launch_rx_neigh_build(d_base, d_off, d_frame_len, n, d_nact, d_list, d_count, d_eng,
+                                      d_out_base, d_out_off, m, slot_bytes, d_out_len, d_built,
+                                      R.D->cus, (hipStream_t)stream);
+    return hip_err(e);
+}
+
+} // extern "C"
