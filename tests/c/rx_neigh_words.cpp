@@ -9,54 +9,13 @@
 // phase, destination phase, flen, then flen frame bytes.
 // Output, per case: uint32 code, out_len, the 24 record bytes, then a 256-byte
 // region pre-filled with 0xA5 in which the reply starts at byte 16 +
-// destination phase.  Every access is checked here: loads aligned and
+// destination phase.  Every access is checked (checked_mem.h): loads aligned and
 // overlapping the frame, stores naturally aligned and inside the reply.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
+#include "checked_mem.h"
 #include "wc_rx_neigh.h"
 
 namespace rn = wc::rn;
 namespace rr = wc::rr;
-
-struct CheckedMem {
-    uint64_t flo, fhi; // the frame: the only bytes a load may overlap
-    uint64_t lo, hi;   // the reply: the only bytes a store may touch
-    uint32_t ld32(uint64_t a) const
-    {
-        if (a % 4 || a + 4 <= flo || a >= fhi) {
-            fprintf(stderr, "load at frame%+lld: misaligned or outside the frame\n", (long long)(a - flo));
-            exit(3);
-        }
-        uint32_t v;
-        memcpy(&v, (const void *)(uintptr_t)a, 4);
-        return v;
-    }
-    void chk(uint64_t a, unsigned w) const
-    {
-        if (a % w || a < lo || a + w > hi) {
-            fprintf(stderr, "store of %u bytes at reply%+lld: misaligned or outside the reply\n", w,
-                    (long long)(a - lo));
-            exit(3);
-        }
-    }
-    void st32(uint64_t a, uint32_t v) const { chk(a, 4), memcpy((void *)(uintptr_t)a, &v, 4); }
-    void st16(uint64_t a, uint32_t v) const
-    {
-        const uint16_t x = (uint16_t)v;
-        chk(a, 2), memcpy((void *)(uintptr_t)a, &x, 2);
-    }
-    void st8(uint64_t a, uint32_t v) const { chk(a, 1), *(uint8_t *)(uintptr_t)a = (uint8_t)v; }
-};
-
-static uint32_t le32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
 
 int main(int argc, char **argv)
 {

@@ -9,69 +9,13 @@
 // ip_id, source phase, destination phase, flen, then flen frame bytes.
 // Output, per case: uint32 action, reply_len, out_len, then a 2304-byte region
 // pre-filled with 0xA5 in which the reply starts at byte 16 + destination
-// phase.  Every access is checked here: loads aligned and overlapping the
+// phase.  Every access is checked (checked_mem.h): loads aligned and overlapping the
 // frame, stores naturally aligned and inside the reply.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
+#include "checked_mem.h"
 #include "wc_rx_reply.h"
 
 namespace rr = wc::rr;
 namespace txb = wc::txb;
-
-struct CheckedMem {
-    uint64_t flo, fhi; // the frame: the only bytes a load may overlap
-    uint64_t lo, hi;   // the reply: the only bytes a store may touch
-    uint32_t ld32(uint64_t a) const
-    {
-        if (a % 4 || a + 4 <= flo || a >= fhi) {
-            fprintf(stderr, "load at frame%+lld: misaligned or outside the frame\n", (long long)(a - flo));
-            exit(3);
-        }
-        uint32_t v;
-        memcpy(&v, (const void *)(uintptr_t)a, 4);
-        return v;
-    }
-    rr::Quad ld128(uint64_t a) const
-    {
-        if (a % 16 || a + 16 <= flo || a >= fhi) {
-            fprintf(stderr, "chunk load at frame%+lld: misaligned or outside the frame\n",
-                    (long long)(a - flo));
-            exit(3);
-        }
-        rr::Quad q;
-        memcpy(&q, (const void *)(uintptr_t)a, 16);
-        return q;
-    }
-    void st128(uint64_t a, const rr::Quad &q) const
-    {
-        chk(a, 16), memcpy((void *)(uintptr_t)a, &q, 16);
-    }
-    void chk(uint64_t a, unsigned w) const
-    {
-        if (a % w || a < lo || a + w > hi) {
-            fprintf(stderr, "store of %u bytes at reply%+lld: misaligned or outside the reply\n", w,
-                    (long long)(a - lo));
-            exit(3);
-        }
-    }
-    void st32(uint64_t a, uint32_t v) const { chk(a, 4), memcpy((void *)(uintptr_t)a, &v, 4); }
-    void st16(uint64_t a, uint32_t v) const
-    {
-        const uint16_t x = (uint16_t)v;
-        chk(a, 2), memcpy((void *)(uintptr_t)a, &x, 2);
-    }
-    void st8(uint64_t a, uint32_t v) const { chk(a, 1), *(uint8_t *)(uintptr_t)a = (uint8_t)v; }
-};
-
-static uint32_t le32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
 
 // in_cksum.c:107-137 on its own
 static uint32_t oc16(const uint8_t *d, uint32_t n)
@@ -153,7 +97,7 @@ int main(int argc, char **argv)
         if (rr::is_reply(act)) {
             const uint64_t fa = (uint64_t)(uintptr_t)fr, fend = fa + flen;
             const uint64_t da = (uint64_t)(uintptr_t)region + 16u + dp;
-            CheckedMem mem{fa, fend, da, da};
+            CheckedMem128<rr::Quad> mem{{fa, fend, da, da}};
             const uint32_t g0 = flen ? rr::frame_dword(mem, fa, fend, 14u) : 0u;
             const uint32_t g1 = flen ? rr::frame_dword(mem, fa, fend, 18u) : 0u;
             const bool v4 = rr::reply_v4(act);

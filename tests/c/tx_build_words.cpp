@@ -8,35 +8,14 @@
 // sock_in, dst_in, slot_bytes, zero_udp, phase, paylen, then paylen payload
 // bytes.  Output, per case: uint32 status, flen, ip_hdr, udp, then a 128-byte
 // region pre-filled with 0xA5 in which the frame starts at byte 16 + phase.
-// Every store is checked here: natural alignment, inside the header bytes.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+// Every store is checked (checked_mem.h): natural alignment, inside the header
+// bytes.
 #include <vector>
 
+#include "checked_mem.h"
 #include "wc_tx_build.h"
 
 namespace txb = wc::txb;
-
-struct CheckedMem {
-    uint64_t lo, hi; // the only bytes a store may touch
-    void chk(uint64_t a, unsigned w) const
-    {
-        if (a % w || a < lo || a + w > hi) {
-            fprintf(stderr, "store of %u bytes at frame%+lld: misaligned or outside the headers\n", w,
-                    (long long)(a - lo));
-            exit(3);
-        }
-    }
-    void st32(uint64_t a, uint32_t v) const { chk(a, 4), memcpy((void *)(uintptr_t)a, &v, 4); }
-    void st16(uint64_t a, uint32_t v) const
-    {
-        const uint16_t x = (uint16_t)v;
-        chk(a, 2), memcpy((void *)(uintptr_t)a, &x, 2);
-    }
-    void st8(uint64_t a, uint32_t v) const { chk(a, 1), *(uint8_t *)(uintptr_t)a = (uint8_t)v; }
-};
 
 int main(int argc, char **argv)
 {
@@ -82,7 +61,8 @@ int main(int argc, char **argv)
         if (built) {
             const txb::Hdr h = txb::headers(x, d, w, t, s, zero_udp, true);
             const uint64_t fa = (uint64_t)(uintptr_t)region + 16u + phase;
-            txb::store_headers(CheckedMem{fa, fa + x.hb}, fa, x.v4, h.h);
+            txb::store_headers(CheckedMem{0, 0, fa, fa + x.hb, "frame", "the headers"}, fa, x.v4,
+                               h.h);
             res[1] = x.flen, res[2] = h.ip_hdr, res[3] = h.udp;
         }
         fwrite(res, 4, 4, out);

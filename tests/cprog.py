@@ -16,3 +16,13 @@ def build(name: str, out_dir: Path) -> Path:
                     "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
                     f"-Wl,-rpath,{ROOT / 'warpcore_amd'}"], check=True)
     return exe
+
+
+def build_words(name: str, out_dir: Path) -> Path:
+    """A host "words" program (tests/c/<name>.cpp over the shared headers of
+    warpcore_amd/csrc, no library) under ASan / UBSan, to be run directly."""
+    exe = Path(out_dir) / name
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", f"-I{ROOT / 'warpcore_amd' / 'csrc'}",
+                    str(ROOT / "tests" / "c" / f"{name}.cpp"), "-o", str(exe)], check=True)
+    return exe

@@ -7,15 +7,14 @@ source and destination.  The program itself refuses a load that does not
 overlap the frame and a store that is misaligned or leaves the reply."""
 import struct
 import subprocess
-from pathlib import Path
 
 import pytest
 
+import cprog
 import rx_neigh_cases as cases
 import rx_neigh_model as model
 import rx_reply_cases as rc
 
-ROOT = Path(__file__).resolve().parent.parent
 REGION = 256
 REC = 8 + 24 + REGION
 OWN = 0xFFFFFFFF
@@ -23,12 +22,7 @@ OWN = 0xFFFFFFFF
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("rxn") / "rx_neigh_words"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all",
-                    f"-I{ROOT / 'warpcore_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "c" / "rx_neigh_words.cpp"), "-o", str(out)], check=True)
-    return out
+    return cprog.build_words("rx_neigh_words", tmp_path_factory.mktemp("rxn"))
 
 
 def run(exe, tmp_path, items):

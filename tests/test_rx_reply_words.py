@@ -6,27 +6,22 @@ destination.  The program itself refuses a load that does not overlap the
 frame and a store that is misaligned or leaves the reply."""
 import struct
 import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import cprog
 import rx_reply_cases as cases
 import rx_reply_model as model
 from oracle import c_oracle
 
-ROOT = Path(__file__).resolve().parent.parent
 REGION = 2304
 OWN = 0xFFFFFFFF
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("rxr") / "rx_reply_words"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall",
-                    f"-I{ROOT / 'warpcore_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "c" / "rx_reply_words.cpp"), "-o", str(out)], check=True)
-    return out
+    return cprog.build_words("rx_reply_words", tmp_path_factory.mktemp("rxr"))
 
 
 def run(exe, tmp_path, items):

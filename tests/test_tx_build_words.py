@@ -5,24 +5,19 @@ and the stores at every 16-byte phase against tests/tx_build_model.py.  The
 program itself refuses a store that is misaligned or leaves the header bytes."""
 import struct
 import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import cprog
 import tx_build_cases as cases
 import tx_build_model as model
 
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("txb") / "tx_build_words"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall",
-                    f"-I{ROOT / 'warpcore_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "c" / "tx_build_words.cpp"), "-o", str(out)], check=True)
-    return out
+    return cprog.build_words("tx_build_words", tmp_path_factory.mktemp("txb"))
 
 
 def run(exe, tmp_path, items):

@@ -148,10 +148,11 @@ def _check_strided_headers(base: torch.Tensor, byte_offset: int, stride: int, le
 
 
 def _check_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor,
-                  kind: int, check: bool, fused: bool = False, in_place: bool = False) -> int:
+                  kind: int, check: bool, fused: bool = False, in_place: bool = False,
+                  indexed: bool = False) -> int:
     """The argument rules of every packet / frame batch call; returns n.
     ``fused``: the IPv4 headers are checked too; ``in_place``: the call writes
-    into ``base``."""
+    into ``base``; ``indexed``: a uint32 list may name the frames."""
     _same_device(base, offsets=offsets, lengths=lengths)
     n = _check_ragged_shapes(offsets, lengths)
     if not base.is_contiguous():
@@ -162,6 +163,8 @@ def _check_ragged(base: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tens
         # one device reduction + sync -- pass check=False on a hot loop whose
         # layout was validated once
         _ragged_bounds(_nbytes(base), offsets, lengths, kind, base if fused else None)
+    if indexed and n > _RX_SELECT_MAX:
+        raise ValueError("at most 2^32 frames (the indices are uint32)")
     return n
 
 
@@ -432,6 +435,15 @@ def _scratch(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.int32, device=device)
 
 
+def _select_scratch(scratch: Optional[torch.Tensor], n: int, device) -> torch.Tensor:
+    """A plan call's rx_select scratch: the caller's, checked, or one allocated here."""
+    if scratch is None:
+        return _scratch(rx_select_scratch(n), device)
+    if _nbytes(scratch) < rx_select_scratch(n) or scratch.device != device:
+        raise ValueError(f"scratch must hold rx_select_scratch(n) bytes on {device}")
+    return scratch
+
+
 def _index_list(out_list: Optional[torch.Tensor], n: int, device) -> Tuple[torch.Tensor, bool]:
     """The uint32 list handed to the library -- ``out_list`` or one of this
     module's -- and whether it is this module's.  It is never empty (an empty
@@ -486,9 +498,7 @@ def rx_deliver_ragged(base: torch.Tensor, offsets: torch.Tensor, frame_lens: tor
     verdict is RX_OK / RX_OK_NO_CKSUM; ``list`` / ``count`` as rx_select gives
     them for ``RX_MASK_DELIVER`` (None, None with ``want_list=False``);
     ``drops`` as rx_verdict_ragged.  No header is parsed on the host."""
-    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
-    if n > _RX_SELECT_MAX:
-        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
     d = base.device
     verdicts = torch.empty(n, dtype=torch.uint8, device=d)
     records = torch.empty((n, RX_RECORD.itemsize), dtype=torch.uint8, device=d)
@@ -715,9 +725,7 @@ def rx_reply_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.T
     list, count)``: ``list`` / ``count`` as rx_select gives them for
     ``RR_MASK_REPLY`` (None, None with ``want_list=False``).  Asynchronous;
     the scratch is allocated here unless given."""
-    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
-    if n > _RX_SELECT_MAX:
-        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
     d = base.device
     _byte_array("verdicts", verdicts, n, d)
     if sock is not None:
@@ -731,10 +739,7 @@ def rx_reply_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.T
     if want_list:
         lst, own = _index_list(out_list, n, d)
         cnt = torch.zeros(1, dtype=torch.int64, device=d)
-        if scratch is None:
-            scratch = _scratch(rx_select_scratch(n), d)
-        elif _nbytes(scratch) < rx_select_scratch(n) or scratch.device != d:
-            raise ValueError(f"scratch must hold rx_select_scratch(n) bytes on {d}")
+        scratch = _select_scratch(scratch, n, d)
     with _on_device(d):
         _check("wc_rx_reply_plan", _lib.active().wc_rx_reply_plan(
             _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(verdicts),
@@ -746,6 +751,52 @@ def rx_reply_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.T
     if want_list and own:
         lst = lst[:n]
     return actions, reply_lens, lst, cnt
+
+
+def _list_args(name: str, plan: str, lst: torch.Tensor, count: torch.Tensor, m: int, n: int,
+               device) -> None:
+    """A list and its count as ``plan``, the call that produced them, gives them."""
+    if not isinstance(lst, torch.Tensor) or not isinstance(count, torch.Tensor) \
+            or lst.device != device or count.device != device:
+        raise ValueError(f"{name} and its count must be device tensors on {device}")
+    if lst.element_size() != 4 or not lst.is_contiguous() or lst.numel() < min(m, n):
+        raise ValueError(f"{name} must be a contiguous 4-byte tensor of >= min(m, n) entries")
+    if count.element_size() != 8 or count.numel() < 1:
+        raise ValueError(f"count must be the 8-byte count of {plan}")
+
+
+def _build_args(plan: str, base: torch.Tensor, n: int, codes_name: str, codes: torch.Tensor,
+                reply_list: torch.Tensor, count: torch.Tensor, engine: torch.Tensor,
+                out: torch.Tensor, out_offsets: torch.Tensor, slot_bytes: int, check: bool,
+                ip_ids: Optional[torch.Tensor] = None):
+    """What rx_reply_build and rx_neigh_build check alike: the code bytes, the
+    table, ``out`` / ``out_offsets`` / ``slot_bytes``, the list of ``plan`` and,
+    under ``check``, every slot inside ``out`` and ``out`` off ``base``.
+    Returns ``(m, out_lens, built)``, the two tensors allocated here."""
+    d = base.device
+    _same_device(base, out=out, out_offsets=out_offsets)  # (the others: by their own checks)
+    _byte_array(codes_name, codes, n, d)
+    _engine_tensor(engine, d)
+    if not out.is_contiguous() or out.element_size() != 1:
+        raise ValueError("out must be a contiguous 1-byte tensor (the replies are written into it)")
+    m = out_offsets.numel()
+    if out_offsets.element_size() != 8 or out_offsets.is_floating_point() \
+            or not out_offsets.is_contiguous() or m > 0xFFFFFFFF:
+        raise ValueError("out_offsets must be contiguous 8-byte integers, at most 2^32 - 1")
+    if not 0 <= int(slot_bytes) <= 0xFFFF:
+        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
+    _list_args("reply_list", plan, reply_list, count, m, n, d)
+    if ip_ids is not None:
+        _byte_array("ip_ids", ip_ids, m, d, 2)
+    if check and m:
+        so = out_offsets.view(torch.int64)
+        if bool((so < 0).any()) or int(so.max()) + int(slot_bytes) > _nbytes(out):
+            raise ValueError("a reply slot [off, off + slot_bytes) runs past out")
+        ob, oe = out.data_ptr(), out.data_ptr() + _nbytes(out)
+        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
+            raise ValueError("out overlaps base: RX frames and reply slots must not overlap")
+    return (m, torch.empty(m, dtype=torch.uint16, device=d),
+            torch.zeros(1, dtype=torch.int64, device=d))
 
 
 def rx_reply_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
@@ -762,38 +813,10 @@ def rx_reply_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.
     built)``, ``built`` a 1-element int64 device tensor.  ``count`` is read on
     the device: no synchronisation.  ``check``: every frame inside ``base`` and
     every slot inside ``out`` (one device reduction and a sync)."""
-    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
-    if n > _RX_SELECT_MAX:
-        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
     d = base.device
-    _same_device(base, actions=actions, reply_list=reply_list, count=count, out=out,
-                 out_offsets=out_offsets, ip_ids=ip_ids)
-    _byte_array("actions", actions, n, d)
-    _engine_tensor(engine, d)
-    if not out.is_contiguous() or out.element_size() != 1:
-        raise ValueError("out must be a contiguous 1-byte tensor (the replies are written into it)")
-    m = out_offsets.numel()
-    if out_offsets.element_size() != 8 or out_offsets.is_floating_point() \
-            or not out_offsets.is_contiguous() or m > 0xFFFFFFFF:
-        raise ValueError("out_offsets must be contiguous 8-byte integers, at most 2^32 - 1")
-    if not 0 <= int(slot_bytes) <= 0xFFFF:
-        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
-    if reply_list.element_size() != 4 or not reply_list.is_contiguous() \
-            or reply_list.numel() < min(m, n):
-        raise ValueError("reply_list must be a contiguous 4-byte tensor of >= min(m, n) entries")
-    if count.element_size() != 8 or count.numel() < 1:
-        raise ValueError("count must be the 8-byte count of rx_reply_plan")
-    if ip_ids is not None:
-        _byte_array("ip_ids", ip_ids, m, d, 2)
-    if check and m:
-        so = out_offsets.view(torch.int64)
-        if bool((so < 0).any()) or int(so.max()) + int(slot_bytes) > _nbytes(out):
-            raise ValueError("a reply slot [off, off + slot_bytes) runs past out")
-        ob, oe = out.data_ptr(), out.data_ptr() + _nbytes(out)
-        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
-            raise ValueError("out overlaps base: RX frames and reply slots must not overlap")
-    out_lens = torch.empty(m, dtype=torch.uint16, device=d)
-    built = torch.zeros(1, dtype=torch.int64, device=d)
+    m, out_lens, built = _build_args("rx_reply_plan", base, n, "actions", actions, reply_list,
+                                     count, engine, out, out_offsets, slot_bytes, check, ip_ids)
     with _on_device(d):
         _check("wc_rx_reply_build", _lib.active().wc_rx_reply_build(
             _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(actions),
@@ -819,16 +842,6 @@ NEIGH_UPDATE = np.dtype([("af", "u1"), ("action", "u1"), ("mac", "u1", 6), ("add
 assert NEIGH_UPDATE.itemsize == 24
 
 
-def _list_args(name: str, lst: torch.Tensor, count: torch.Tensor, m: int, n: int, device) -> None:
-    if not isinstance(lst, torch.Tensor) or not isinstance(count, torch.Tensor) \
-            or lst.device != device or count.device != device:
-        raise ValueError(f"{name} and its count must be device tensors on {device}")
-    if lst.element_size() != 4 or not lst.is_contiguous() or lst.numel() < min(m, n):
-        raise ValueError(f"{name} must be a contiguous 4-byte tensor of >= min(m, n) entries")
-    if count.element_size() != 8 or count.numel() < 1:
-        raise ValueError("count must be the 8-byte count of rx_neigh_plan")
-
-
 def rx_neigh_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
                   actions: torch.Tensor, engine: torch.Tensor, want_replies: bool = True,
                   want_updates: bool = True, stream=None, check: bool = True,
@@ -840,9 +853,7 @@ def rx_neigh_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.T
     the lists / counts as rx_select gives them for ``RN_MASK_REPLY`` and
     ``RN_MASK_UPDATE`` (None, None where not wanted).  Asynchronous; the
     scratch is allocated here unless given."""
-    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
-    if n > _RX_SELECT_MAX:
-        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
     d = base.device
     _byte_array("actions", actions, n, d)
     _engine_tensor(engine, d)
@@ -854,13 +865,7 @@ def rx_neigh_plan(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.T
     if want_updates:
         ul, _ = _index_list(None, n, d)
         uc = torch.zeros(1, dtype=torch.int64, device=d)
-    if want_replies or want_updates:
-        if scratch is None:
-            scratch = _scratch(rx_select_scratch(n), d)
-        elif _nbytes(scratch) < rx_select_scratch(n) or scratch.device != d:
-            raise ValueError(f"scratch must hold rx_select_scratch(n) bytes on {d}")
-    else:
-        scratch = None
+    scratch = _select_scratch(scratch, n, d) if want_replies or want_updates else None
     with _on_device(d):
         _check("wc_rx_neigh_plan", _lib.active().wc_rx_neigh_plan(
             _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(actions),
@@ -879,15 +884,13 @@ def rx_neigh_updates(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torc
     min(count, m)`` that of frame ``update_list[j]``, the rest all zero (on the
     host: ``.cpu().numpy().view(NEIGH_UPDATE)``).  In ring order: apply them in
     order.  ``count`` is read on the device: no synchronisation."""
-    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
-    if n > _RX_SELECT_MAX:
-        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
     m = int(m)
     if not 0 <= m <= 0xFFFFFFFF:
         raise ValueError("m is a uint32")
     d = base.device
     _byte_array("nact", nact, n, d)
-    _list_args("update_list", update_list, count, m, n, d)
+    _list_args("update_list", "rx_neigh_plan", update_list, count, m, n, d)
     upd = torch.empty((m, NEIGH_UPDATE.itemsize), dtype=torch.uint8, device=d)
     with _on_device(d):
         _check("wc_rx_neigh_updates", _lib.active().wc_rx_neigh_updates(
@@ -906,32 +909,10 @@ def rx_neigh_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.
     m)``, ``m = out_offsets.numel()``, answers frame ``reply_list[j]`` at
     ``out[out_offsets[j]]``.  Returns ``(out_lens uint16 -- 0 where no reply was
     written --, built)``."""
-    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check)
-    if n > _RX_SELECT_MAX:
-        raise ValueError("at most 2^32 frames (the indices are uint32)")
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
     d = base.device
-    _same_device(base, nact=nact, reply_list=reply_list, count=count, out=out,
-                 out_offsets=out_offsets)
-    _byte_array("nact", nact, n, d)
-    _engine_tensor(engine, d)
-    if not out.is_contiguous() or out.element_size() != 1:
-        raise ValueError("out must be a contiguous 1-byte tensor (the replies are written into it)")
-    m = out_offsets.numel()
-    if out_offsets.element_size() != 8 or out_offsets.is_floating_point() \
-            or not out_offsets.is_contiguous() or m > 0xFFFFFFFF:
-        raise ValueError("out_offsets must be contiguous 8-byte integers, at most 2^32 - 1")
-    if not 0 <= int(slot_bytes) <= 0xFFFF:
-        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
-    _list_args("reply_list", reply_list, count, m, n, d)
-    if check and m:
-        so = out_offsets.view(torch.int64)
-        if bool((so < 0).any()) or int(so.max()) + int(slot_bytes) > _nbytes(out):
-            raise ValueError("a reply slot [off, off + slot_bytes) runs past out")
-        ob, oe = out.data_ptr(), out.data_ptr() + _nbytes(out)
-        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
-            raise ValueError("out overlaps base: RX frames and reply slots must not overlap")
-    out_lens = torch.empty(m, dtype=torch.uint16, device=d)
-    built = torch.zeros(1, dtype=torch.int64, device=d)
+    m, out_lens, built = _build_args("rx_neigh_plan", base, n, "nact", nact, reply_list, count,
+                                     engine, out, out_offsets, slot_bytes, check)
     with _on_device(d):
         _check("wc_rx_neigh_build", _lib.active().wc_rx_neigh_build(
             _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(nact),

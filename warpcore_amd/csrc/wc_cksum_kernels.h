@@ -116,6 +116,13 @@ namespace wc {
 // correct (wc_cksum_api.cpp grid_for, the ragged launchers).
 constexpr uint64_t kMaxGridBlocks = (1ull << 24) - 1;
 
+// The grid of a tile kernel: one one-wave workgroup per tile of 64 frames.
+inline int tile_grid(uint64_t n)
+{
+    const uint64_t tiles = (n + 63) / 64;
+    return (int)(tiles > kMaxGridBlocks ? kMaxGridBlocks : tiles ? tiles : 1);
+}
+
 struct LaunchArgs {
     const void *base;
     uint64_t stride;

@@ -31,8 +31,11 @@
 //
 // Kernels: wc_k_strided.hip (group-per-packet, strided batches), wc_k_flat.hip
 // (chunk-balanced flat kernel), wc_k_seg.hip (segmented-prefix tile kernel
-// with its grouped and flat paths), wc_k_synth.hip (synthetic bytes).  Every
-// helper here has internal linkage, so each kernel translation unit carries
+// with its grouped and flat paths), wc_k_synth.hip (synthetic bytes).  The
+// frame writers (wc_k_txbuild.hip, wc_k_rxreply.hip, wc_k_rxneigh.hip) take
+// their global-memory accessor (GlobalMem) and the list kernels' frame
+// (list_entry, list_meta, block_count_add, list_grid) from the end of this
+// file.  Every helper here has internal linkage, so each kernel translation unit carries
 // its own copy of the device tables.
 #pragma once
 
@@ -576,6 +579,113 @@ __device__ __forceinline__ void meta_load(const uint64_t *__restrict__ offs,
     off = offs[pc];
     const uint32_t l = lens[pc];
     len = v ? l : 0u;
+}
+
+// Global memory at addresses computed as integers, natural alignment: the
+// accessor the shared frame statements (wc_tx_build.h, wc_rx_reply.h,
+// wc_rx_neigh.h) take as `Mem` on the device.
+typedef uint32_t __attribute__((address_space(1))) *gst32_ptr;
+typedef uint16_t __attribute__((address_space(1))) *gst16_ptr;
+typedef uint8_t __attribute__((address_space(1))) *gst8_ptr;
+typedef const uint32_t __attribute__((address_space(1))) *gld32_ptr;
+
+struct GlobalMem {
+    __device__ __forceinline__ uint32_t ld32(uint64_t a) const { return *(gld32_ptr)(uintptr_t)a; }
+    __device__ __forceinline__ void st32(uint64_t a, uint32_t v) const
+    {
+        *(gst32_ptr)(uintptr_t)a = v;
+    }
+    __device__ __forceinline__ void st16(uint64_t a, uint32_t v) const
+    {
+        *(gst16_ptr)(uintptr_t)a = (uint16_t)v;
+    }
+    __device__ __forceinline__ void st8(uint64_t a, uint32_t v) const
+    {
+        *(gst8_ptr)(uintptr_t)a = (uint8_t)v;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// The list kernels' frame (k_rx_reply_build, k_rx_neigh_updates,
+// k_rx_neigh_build): entry j < MIN(*count, m) of a device list names a frame,
+// and the kernel strides over all m outputs.
+
+__device__ __forceinline__ uint64_t list_limit(const unsigned long long *__restrict__ count,
+                                               uint32_t m)
+{
+    const uint64_t cnt = *count;
+    return cnt < m ? cnt : (uint64_t)m;
+}
+
+// Entry j, or ~0 past the list: 64 bits wide, so that no n up to 2^32 makes a
+// past-the-list entry name a frame.
+__device__ __forceinline__ uint64_t list_entry(const uint32_t *__restrict__ list, uint64_t j,
+                                               uint64_t lim)
+{
+    return j < lim ? (uint64_t)list[j] : ~0ull;
+}
+
+// What a list kernel reads about an entry in front of the frame itself: the
+// code byte, the frame's offset and length.  live: the entry names a frame.
+struct ListMeta {
+    uint64_t off;
+    uint32_t act, flen;
+    bool live;
+};
+
+__device__ __forceinline__ ListMeta list_meta(uint64_t idx, uint64_t n,
+                                              const uint8_t *__restrict__ code,
+                                              const uint64_t *__restrict__ offs,
+                                              const uint16_t *__restrict__ flens)
+{
+    ListMeta t{0u, 0u, 0u, false};
+    if (idx < n) {
+        t.act = code[idx];
+        t.off = offs[idx];
+        t.flen = flens[idx];
+        t.live = true;
+    }
+    return t;
+}
+
+// *total += the workgroup's sum of its WAVES waves' totals (wave-uniform
+// values): one atomic per workgroup, none where the sum is 0.  Every thread of
+// the workgroup calls it, once.
+template <int WAVES>
+__device__ __forceinline__ void block_count_add(uint32_t wave_total,
+                                                unsigned long long *__restrict__ total)
+{
+    __shared__ uint32_t nb[WAVES];
+    if ((threadIdx.x & 63u) == 0u)
+        nb[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int k = 0; k < WAVES; ++k)
+            s += nb[k];
+        if (s)
+            atomicAdd(total, (unsigned long long)s);
+    }
+}
+
+// The grid of a list kernel of THREADS threads that takes PER entries per
+// workgroup and step: what the device's `cus` compute units hold at once (0:
+// no cap) -- a workgroup that had to wait for a slot would start its share
+// when the others are done -- and no more than m needs.  One occupancy query
+// per kernel.
+template <auto KERNEL, int THREADS, int PER>
+int list_grid(uint32_t m, int cus)
+{
+    static const int per_cu = [] {
+        int k = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, KERNEL, THREADS, 0) != hipSuccess ||
+            k < 1)
+            k = 1;
+        return k;
+    }();
+    const uint64_t blocks = ((uint64_t)m + PER - 1) / PER;
+    const uint64_t cap = cus > 0 ? (uint64_t)cus * per_cu : kMaxGridBlocks;
+    return (int)std::min<uint64_t>(cap, std::max<uint64_t>(1, blocks));
 }
 
 } // namespace

@@ -27,7 +27,7 @@
 // (rn::record_of, rn::build), so a stale byte gives an empty record or length 0,
 // never an access outside the frame or the slot.  Stores are plain vector
 // stores: aligned dwords inside the reply, byte / 2-byte stores at its two ends
-// (rn::store_words), so a neighbouring slot that shares a dword keeps every
+// (txb::store_words), so a neighbouring slot that shares a dword keeps every
 // byte of its own.  The advertisement's checksum is formed in registers; its 37
 // words cannot wrap a uint32.  The only atomic is the built count's, one per
 // workgroup with a built reply.
@@ -37,27 +37,6 @@
 
 namespace wc {
 namespace {
-
-typedef uint32_t __attribute__((address_space(1))) *nst32_ptr;
-typedef uint16_t __attribute__((address_space(1))) *nst16_ptr;
-typedef uint8_t __attribute__((address_space(1))) *nst8_ptr;
-typedef const uint32_t __attribute__((address_space(1))) *nld32_ptr;
-
-struct NeighMem { // rr::frame_dword's and rn::store_words' accesses: global memory
-    __device__ __forceinline__ uint32_t ld32(uint64_t a) const { return *(nld32_ptr)(uintptr_t)a; }
-    __device__ __forceinline__ void st32(uint64_t a, uint32_t v) const
-    {
-        *(nst32_ptr)(uintptr_t)a = v;
-    }
-    __device__ __forceinline__ void st16(uint64_t a, uint32_t v) const
-    {
-        *(nst16_ptr)(uintptr_t)a = (uint16_t)v;
-    }
-    __device__ __forceinline__ void st8(uint64_t a, uint32_t v) const
-    {
-        *(nst8_ptr)(uintptr_t)a = (uint8_t)v;
-    }
-};
 
 constexpr int kRnSpan = 15; // XCD super-blocks of 2^15 tiles, as the reply plan's
 
@@ -87,17 +66,10 @@ k_rx_neigh_plan(const uint8_t *__restrict__ base, const uint64_t *__restrict__ o
         const bool host = valid && action[valid ? p : 0] == rr::kHost;
         uint32_t code = rn::kNone;
         if (__ballot(host)) {
-            // Frame bytes 0..55 as fourteen dwords (k_rx_reply_plan's windows)
             u32x4 c[5];
             rx_load(fa, flen, host, zero, c);
-            const uint32_t sf = (uint32_t)(fa & 15u);
-            const u32x4 z4 = {0u, 0u, 0u, 0u};
             uint32_t A[5], B[5], C[4]; // frame bytes 0..19, 20..39, 40..55
-            win_rot(c[0], c[1], c[2], sf, A);
-            const uint32_t o1 = sf + 20u, o2 = sf + 40u;
-            const bool j1 = o1 >= 32u, j2 = o2 >= 48u;
-            win_rot(j1 ? c[2] : c[1], j1 ? c[3] : c[2], j1 ? c[4] : c[3], o1 & 15u, B);
-            win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, C);
+            rx_words56(c, fa, A, B, C);
 
             rn::Look f;
             f.action = host ? rr::kHost : rn::kNone;
@@ -124,30 +96,6 @@ k_rx_neigh_plan(const uint8_t *__restrict__ base, const uint64_t *__restrict__ o
 
 constexpr uint32_t kNeighBlock = 256;
 
-// What the list kernels read about entry j in front of the frame itself: the
-// code byte, the frame's offset and length.  `idx` is the list entry, ~0 past
-// MIN(*count, m); live: the entry names a frame.
-struct NeighMeta {
-    uint64_t off;
-    uint32_t act, flen;
-    bool live;
-};
-
-__device__ __forceinline__ NeighMeta neigh_meta(uint64_t idx, uint64_t n,
-                                                const uint8_t *__restrict__ nact,
-                                                const uint64_t *__restrict__ offs,
-                                                const uint16_t *__restrict__ flens)
-{
-    NeighMeta t{0u, 0u, 0u, false};
-    if (idx < n) {
-        t.act = nact[idx];
-        t.off = offs[idx];
-        t.flen = flens[idx];
-        t.live = true;
-    }
-    return t;
-}
-
 __global__ void __launch_bounds__(kNeighBlock)
 k_rx_neigh_updates(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
                    const uint16_t *__restrict__ flens, uint64_t n,
@@ -155,16 +103,15 @@ k_rx_neigh_updates(const uint8_t *__restrict__ base, const uint64_t *__restrict_
                    const unsigned long long *__restrict__ count, uint32_t m,
                    uint32_t *__restrict__ upd)
 {
-    const uint64_t cnt = *count;
-    const uint64_t lim = cnt < m ? cnt : (uint64_t)m;
-    const NeighMem mem{};
+    const uint64_t lim = list_limit(count, m);
+    const GlobalMem mem{};
     const uint64_t S = (uint64_t)gridDim.x * kNeighBlock;
     uint64_t j = (uint64_t)blockIdx.x * kNeighBlock + threadIdx.x;
-    NeighMeta cur = neigh_meta(j < lim ? list[j] : ~0ull, n, nact, offs, flens);
-    uint64_t idx_n = j + S < lim ? list[j + S] : ~0ull;
+    ListMeta cur = list_meta(list_entry(list, j, lim), n, nact, offs, flens);
+    uint64_t idx_n = list_entry(list, j + S, lim);
     for (; j < m; j += S) {
-        const NeighMeta nxt = neigh_meta(idx_n, n, nact, offs, flens);
-        idx_n = j + 2 * S < lim ? list[j + 2 * S] : ~0ull;
+        const ListMeta nxt = list_meta(idx_n, n, nact, offs, flens);
+        idx_n = list_entry(list, j + 2 * S, lim);
         uint32_t u[6] = {0u, 0u, 0u, 0u, 0u, 0u};
         if (cur.live && rn::is_update(cur.act))
             rn::record_of(mem, (uint64_t)(uintptr_t)base + cur.off, cur.flen, cur.act, u);
@@ -185,20 +132,18 @@ k_rx_neigh_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
                  uint32_t slot_bytes, uint16_t *__restrict__ out_len,
                  unsigned long long *__restrict__ built)
 {
-    __shared__ uint32_t nb[kNeighBlock / 64];
-    const uint64_t cnt = *count;
-    const uint64_t lim = cnt < m ? cnt : (uint64_t)m;
-    const NeighMem mem{};
+    const uint64_t lim = list_limit(count, m);
+    const GlobalMem mem{};
     uint32_t nbuilt = 0;
     const uint64_t S = (uint64_t)gridDim.x * kNeighBlock;
     uint64_t j = (uint64_t)blockIdx.x * kNeighBlock + threadIdx.x;
-    NeighMeta cur = neigh_meta(j < lim ? list[j] : ~0ull, n, nact, offs, flens);
+    ListMeta cur = list_meta(list_entry(list, j, lim), n, nact, offs, flens);
     uint64_t ooff = j < m ? out_off[j] : 0u;
-    uint64_t idx_n = j + S < lim ? list[j + S] : ~0ull;
+    uint64_t idx_n = list_entry(list, j + S, lim);
     for (; j < m; j += S) {
-        const NeighMeta nxt = neigh_meta(idx_n, n, nact, offs, flens);
+        const ListMeta nxt = list_meta(idx_n, n, nact, offs, flens);
         const uint64_t ooff_n = j + S < m ? out_off[j + S] : 0u;
-        idx_n = j + 2 * S < lim ? list[j + 2 * S] : ~0ull;
+        idx_n = list_entry(list, j + 2 * S, lim);
         uint32_t len = 0;
         if (cur.live && rn::is_reply(cur.act))
             len = rn::build(mem, (uint64_t)(uintptr_t)base + cur.off, cur.flen, cur.act, eng,
@@ -208,35 +153,7 @@ k_rx_neigh_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
         cur = nxt;
         ooff = ooff_n;
     }
-    const uint32_t ws = group_sum<64>(nbuilt);
-    if ((threadIdx.x & 63u) == 0u)
-        nb[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (uint32_t k = 0; k < kNeighBlock / 64; ++k)
-            s += nb[k];
-        if (s)
-            atomicAdd(built, (unsigned long long)s);
-    }
-}
-
-// The list kernels' grid: what the device holds at once, striding over m (a
-// workgroup that had to wait for a slot would start when the others are done).
-template <class K>
-int neigh_per_cu(K kernel)
-{
-    int k = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kernel, kNeighBlock, 0) != hipSuccess || k < 1)
-        k = 1;
-    return k;
-}
-
-int neigh_grid(uint32_t m, int cus, int per_cu)
-{
-    const uint64_t blocks = ((uint64_t)m + kNeighBlock - 1) / kNeighBlock;
-    const uint64_t cap = cus > 0 ? (uint64_t)cus * per_cu : kMaxGridBlocks;
-    return (int)std::min<uint64_t>(cap, std::max<uint64_t>(1, blocks));
+    block_count_add<kNeighBlock / 64>(group_sum<64>(nbuilt), built);
 }
 
 } // namespace
@@ -245,9 +162,7 @@ hipError_t launch_rx_neigh_plan(const void *base, const uint64_t *offs, const ui
                                 uint64_t n, const uint8_t *action, const void *eng, uint8_t *nact,
                                 hipStream_t st)
 {
-    const uint64_t tiles = (n + 63) / 64;
-    const int grid = (int)std::min<uint64_t>(kMaxGridBlocks, std::max<uint64_t>(1, tiles));
-    hipLaunchKernelGGL(k_rx_neigh_plan, dim3(grid), dim3(64), 0, st, (const uint8_t *)base, offs,
+    hipLaunchKernelGGL(k_rx_neigh_plan, dim3(tile_grid(n)), dim3(64), 0, st, (const uint8_t *)base, offs,
                        flens, n, action, (const uint32_t *)eng, nact);
     return hipGetLastError();
 }
@@ -257,8 +172,7 @@ hipError_t launch_rx_neigh_updates(const void *base, const uint64_t *offs, const
                                    const uint64_t *count, uint32_t m, void *upd, int cus,
                                    hipStream_t st)
 {
-    static const int per = neigh_per_cu(k_rx_neigh_updates);
-    const int grid = neigh_grid(m, cus, per);
+    const int grid = list_grid<k_rx_neigh_updates, kNeighBlock, kNeighBlock>(m, cus);
     hipLaunchKernelGGL(k_rx_neigh_updates, dim3(grid), dim3(kNeighBlock), 0, st,
                        (const uint8_t *)base, offs, flens, n, nact, list,
                        (const unsigned long long *)count, m, (uint32_t *)upd);
@@ -271,8 +185,7 @@ hipError_t launch_rx_neigh_build(const void *base, const uint64_t *offs, const u
                                  const uint64_t *out_off, uint32_t m, uint32_t slot_bytes,
                                  uint16_t *out_len, uint64_t *built, int cus, hipStream_t st)
 {
-    static const int per = neigh_per_cu(k_rx_neigh_build);
-    const int grid = neigh_grid(m, cus, per);
+    const int grid = list_grid<k_rx_neigh_build, kNeighBlock, kNeighBlock>(m, cus);
     hipLaunchKernelGGL(k_rx_neigh_build, dim3(grid), dim3(kNeighBlock), 0, st,
                        (const uint8_t *)base, offs, flens, n, nact, list,
                        (const unsigned long long *)count, (const uint32_t *)eng,

@@ -63,14 +63,9 @@
 namespace wc {
 namespace {
 
-typedef uint32_t __attribute__((address_space(1))) *gst32_ptr;
-typedef uint16_t __attribute__((address_space(1))) *gst16_ptr;
-typedef uint8_t __attribute__((address_space(1))) *gst8_ptr;
-typedef const uint32_t __attribute__((address_space(1))) *gld32_ptr;
 typedef u32x4 __attribute__((address_space(1))) *gst128_ptr;
 
-struct ReplyMem { // rr::copy_dword's and txb::store_headers' accesses: global memory
-    __device__ __forceinline__ uint32_t ld32(uint64_t a) const { return *(gld32_ptr)(uintptr_t)a; }
+struct ReplyMem : GlobalMem { // and rr::copy_chunk's accesses on rr::Quad
     __device__ __forceinline__ rr::Quad ld128(uint64_t a) const
     {
         const u32x4 v = load_chunk<false>(a);
@@ -80,24 +75,7 @@ struct ReplyMem { // rr::copy_dword's and txb::store_headers' accesses: global m
     {
         *(gst128_ptr)(uintptr_t)a = u32x4{q.x, q.y, q.z, q.w};
     }
-    __device__ __forceinline__ void st32(uint64_t a, uint32_t v) const
-    {
-        *(gst32_ptr)(uintptr_t)a = v;
-    }
-    __device__ __forceinline__ void st16(uint64_t a, uint32_t v) const
-    {
-        *(gst16_ptr)(uintptr_t)a = (uint16_t)v;
-    }
-    __device__ __forceinline__ void st8(uint64_t a, uint32_t v) const
-    {
-        *(gst8_ptr)(uintptr_t)a = (uint8_t)v;
-    }
 };
-
-__device__ __forceinline__ uint32_t be16(uint32_t x) // a stored 16-bit field, host order
-{
-    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
-}
 
 constexpr int kRrSpan = 15; // XCD super-blocks of 2^15 tiles, as the RX verdict's
 
@@ -135,18 +113,10 @@ k_rx_reply_plan(const uint8_t *__restrict__ base, const uint64_t *__restrict__ o
         const uint32_t vd = verdict[pc];
         const uint32_t sk = sock ? sock[pc] : 0u;
 
-        // Frame bytes 0..55 as fourteen dwords: three 20-byte windows rotated
-        // out of the five chunks (frame_hdr's way).
         u32x4 c[5];
         rx_load(fa, flen, valid, zero, c);
-        const uint32_t sf = (uint32_t)(fa & 15u);
-        const u32x4 z4 = {0u, 0u, 0u, 0u};
         uint32_t A[5], B[5], C[4]; // frame bytes 0..19, 20..39, 40..55
-        win_rot(c[0], c[1], c[2], sf, A);
-        const uint32_t o1 = sf + 20u, o2 = sf + 40u;
-        const bool j1 = o1 >= 32u, j2 = o2 >= 48u;
-        win_rot(j1 ? c[2] : c[1], j1 ? c[3] : c[2], j1 ? c[4] : c[3], o1 & 15u, B);
-        win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, C);
+        rx_words56(c, fa, A, B, C);
 
         const RxHdr x = rx_hdr(A[3], A[4], B[0], flen);
         rr::Frame f;
@@ -156,7 +126,7 @@ k_rx_reply_plan(const uint8_t *__restrict__ base, const uint64_t *__restrict__ o
         f.v4 = x.v4;
         f.hl = x.hl;
         f.proto = x.proto;
-        f.ip_len = x.v4 ? be16(A[4]) : be16(A[4] >> 16); // bytes 16..17 / 18..19
+        f.ip_len = txb::bswap16(x.v4 ? A[4] : A[4] >> 16); // bytes 16..17 / 18..19
         // IPv4 src @26, dst @30; IPv6 src @22..37, dst @38..53
         uint32_t src[4], dst[4];
         src[0] = x.v4 ? (B[1] >> 16) | (B[2] << 16) : (B[0] >> 16) | (B[1] << 16);
@@ -216,36 +186,6 @@ k_rx_reply_plan(const uint8_t *__restrict__ base, const uint64_t *__restrict__ o
 // (profiles/ab_rxreply_build.log).
 constexpr uint32_t kBuildWaves = 8;
 
-// What the build reads about reply j in front of the frame itself: its list
-// entry's action, frame offset and length, its slot and ip->id.  `idx` is the
-// list entry, ~0 past MIN(*count, m); live: the entry names a frame.
-struct BuildMeta {
-    uint64_t off, ooff;
-    uint32_t act, flen, ipid;
-    bool live;
-};
-
-__device__ __forceinline__ BuildMeta build_meta(uint32_t idx, uint64_t j, uint32_t m, uint64_t n,
-                                                const uint8_t *__restrict__ action,
-                                                const uint64_t *__restrict__ offs,
-                                                const uint16_t *__restrict__ flens,
-                                                const uint64_t *__restrict__ out_off,
-                                                const uint16_t *__restrict__ ip_id)
-{
-    BuildMeta t{0u, 0u, 0u, 0u, 0u, false};
-    if (j < m) {
-        t.ooff = out_off[j];
-        t.ipid = ip_id ? (uint32_t)ip_id[j] : 0u;
-        if (idx < n) {
-            t.act = action[idx];
-            t.off = offs[idx];
-            t.flen = flens[idx];
-            t.live = true;
-        }
-    }
-    return t;
-}
-
 __global__ void __launch_bounds__(64 * kBuildWaves)
 k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
                  const uint16_t *__restrict__ flens, uint64_t n,
@@ -255,11 +195,9 @@ k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
                  uint32_t slot_bytes, const uint16_t *__restrict__ ip_id,
                  uint16_t *__restrict__ out_len, unsigned long long *__restrict__ built)
 {
-    __shared__ uint32_t nb[kBuildWaves];
     const int lane = threadIdx.x & 63;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t cnt = *count;
-    const uint64_t lim = cnt < m ? cnt : (uint64_t)m;
+    const uint64_t lim = list_limit(count, m);
     const uint32_t mtu = rr::eng_mtu(eng);
     const ReplyMem mem{};
     uint32_t nbuilt = 0; // wave-uniform
@@ -271,12 +209,18 @@ k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
     // of the reply being built.
     const uint64_t S = (uint64_t)gridDim.x * kBuildWaves;
     uint64_t j = (uint64_t)blockIdx.x * kBuildWaves + w;
-    BuildMeta cur = build_meta(j < lim ? list[j] : 0xFFFFFFFFu, j, m, n, action, offs, flens,
-                               out_off, ip_id);
-    uint32_t idx_n = j + S < lim ? list[j + S] : 0xFFFFFFFFu;
+    // (the slot and ip->id of reply j are read one reply ahead too)
+    auto slot_of = [&](uint64_t k) { return k < m ? out_off[k] : 0u; };
+    auto ipid_of = [&](uint64_t k) { return ip_id && k < m ? (uint32_t)ip_id[k] : 0u; };
+    ListMeta cur = list_meta(list_entry(list, j, lim), n, action, offs, flens);
+    uint64_t ooff = slot_of(j);
+    uint32_t ipid = ipid_of(j);
+    uint64_t idx_n = list_entry(list, j + S, lim);
     for (; j < m; j += S) {
-        const BuildMeta nxt = build_meta(idx_n, j + S, m, n, action, offs, flens, out_off, ip_id);
-        idx_n = j + 2 * S < lim ? list[j + 2 * S] : 0xFFFFFFFFu;
+        const ListMeta nxt = list_meta(idx_n, n, action, offs, flens);
+        const uint64_t ooff_n = slot_of(j + S);
+        const uint32_t ipid_n = ipid_of(j + S);
+        idx_n = list_entry(list, j + 2 * S, lim);
         uint32_t len = 0;
         if (cur.live && rr::is_reply(cur.act)) { // (wave-uniform branches throughout)
             const uint32_t act = cur.act, flen = cur.flen;
@@ -287,11 +231,11 @@ k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
             const uint32_t g1 = rr::frame_dword(mem, fa, fend, 18u);
             const bool v4 = rr::reply_v4(act);
             const uint32_t hl = v4 ? ((g0 & 15u) * 4u) : 40u;
-            const uint32_t ip_len = v4 ? be16(g0 >> 16) : be16(g1);
+            const uint32_t ip_len = txb::bswap16(v4 ? g0 >> 16 : g1);
             const rr::Reply r = rr::reply_of(act, hl, ip_len, flen, mtu, slot_bytes);
             if (rr::is_reply(r.action)) {
                 const rr::Req q = rr::request_of(mem, fa, fend, act, hl);
-                const uint64_t da = (uint64_t)(uintptr_t)out_base + cur.ooff;
+                const uint64_t da = (uint64_t)(uintptr_t)out_base + ooff;
                 const uint64_t dd = da + (v4 ? 42u : 62u), sa = fa + r.s0;
                 const uint32_t nd = rr::copy_dwords(dd, r.dlen);
                 const rr::Chunks ch = rr::copy_chunks(dd, r.dlen);
@@ -305,7 +249,7 @@ k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
                     acc += rr::copy_dword(mem, sa, dd, r.dlen, i);
                 const uint32_t data = rr::fold16(group_sum<64>(acc));
                 uint32_t h[16];
-                rr::headers(r, q, eng, cur.ipid, data, h);
+                rr::headers(r, q, eng, ipid, data, h);
                 if (lane == 0)
                     txb::store_headers(mem, da, v4, h);
                 len = r.len;
@@ -315,17 +259,10 @@ k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
             out_len[j] = (uint16_t)len;
         nbuilt += len != 0u;
         cur = nxt;
+        ooff = ooff_n;
+        ipid = ipid_n;
     }
-    if (lane == 0)
-        nb[w] = nbuilt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (uint32_t k = 0; k < kBuildWaves; ++k)
-            s += nb[k];
-        if (s)
-            atomicAdd(built, (unsigned long long)s);
-    }
+    block_count_add<kBuildWaves>(nbuilt, built);
 }
 
 } // namespace
@@ -335,8 +272,7 @@ hipError_t launch_rx_reply_plan(const void *base, const uint64_t *offs, const ui
                                 const void *eng, uint32_t slot_bytes, uint8_t *action,
                                 uint16_t *reply_len, bool nt, hipStream_t st)
 {
-    const uint64_t tiles = (n + 63) / 64;
-    const int grid = (int)std::min<uint64_t>(kMaxGridBlocks, std::max<uint64_t>(1, tiles));
+    const int grid = tile_grid(n);
     if (nt)
         hipLaunchKernelGGL((k_rx_reply_plan<true>), dim3(grid), dim3(64), 0, st,
                            (const uint8_t *)base, offs, flens, n, verdict, sock,
@@ -355,18 +291,7 @@ hipError_t launch_rx_reply_build(const void *base, const uint64_t *offs, const u
                                  const uint16_t *ip_id, uint16_t *out_len, uint64_t *built,
                                  int cus, hipStream_t st)
 {
-    // The grid: what the device holds at once (a workgroup that had to wait for
-    // a slot would start its share of the replies when the others are done).
-    static const int per_cu = [] {
-        int k = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, k_rx_reply_build, 64 * kBuildWaves, 0) !=
-                hipSuccess || k < 1)
-            k = 1;
-        return k;
-    }();
-    const uint64_t blocks = ((uint64_t)m + kBuildWaves - 1) / kBuildWaves;
-    const uint64_t cap = cus > 0 ? (uint64_t)cus * per_cu : kMaxGridBlocks;
-    const int grid = (int)std::min<uint64_t>(cap, std::max<uint64_t>(1, blocks));
+    const int grid = list_grid<k_rx_reply_build, 64 * kBuildWaves, kBuildWaves>(m, cus);
     hipLaunchKernelGGL(k_rx_reply_build, dim3(grid), dim3(64 * kBuildWaves), 0, st, (const uint8_t *)base, offs,
                        flens, n, action, list, (const unsigned long long *)count,
                        (const uint32_t *)eng, (uint8_t *)out_base, out_off, m, slot_bytes, ip_id,

@@ -138,19 +138,16 @@ __device__ __forceinline__ TxParse tx_parse_slow(uint64_t fa, uint32_t flen, boo
     return tx_decide(flen, valid, f.x, f.g0, f.ipck, f.f_ip, zero_udp);
 }
 
-typedef uint16_t __attribute__((address_space(1))) *gu16_ptr;
-typedef uint8_t __attribute__((address_space(1))) *gu8_ptr;
-
 // A native uint16 stored raw at any address parity, as the reference's
 // `ip->cksum = ...` / `udp->cksum = ...` leave it in memory.
 __device__ __forceinline__ void store_raw16(uint64_t a, uint32_t v)
 {
     if (a & 1u) {
-        gu8_ptr p = (gu8_ptr)(uintptr_t)a;
+        gst8_ptr p = (gst8_ptr)(uintptr_t)a;
         p[0] = (uint8_t)v;
         p[1] = (uint8_t)(v >> 8);
     } else {
-        *(gu16_ptr)(uintptr_t)a = (uint16_t)v;
+        *(gst16_ptr)(uintptr_t)a = (uint16_t)v;
     }
 }
 
@@ -245,8 +242,7 @@ hipError_t launch_tx_seal(void *base, const uint64_t *offs, const uint16_t *flen
                           uint32_t flags, uint8_t *status, uint16_t *out_ip, uint16_t *out_udp,
                           uint64_t *errors, bool nt, hipStream_t st)
 {
-    const uint64_t tiles = (n + 63) / 64;
-    const int grid = (int)std::min<uint64_t>(kMaxGridBlocks, std::max<uint64_t>(1, tiles));
+    const int grid = tile_grid(n);
     const uint32_t zu = (flags & kTxZeroUdp) ? 1u : 0u;
     const bool store = !(flags & kTxNoStore);
 #define WC_TX(N, S)                                                            \

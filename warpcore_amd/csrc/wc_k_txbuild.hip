@@ -25,7 +25,8 @@
 //   3. the two checksums from registers: ip_cksum of the ten IPv4 header
 //      words, and fold_not(S_pseudo + S_udphdr + fold(S_payload)).
 //   4. with every load of the tile back (s_waitcnt vmcnt(0)), plain vector
-//      stores of the 42 or 62 header bytes (txb::store_headers).
+//      stores of the 42 or 62 header bytes (txb::store_headers, through
+//      wc_device.h's GlobalMem).
 //
 // No 32-bit sum wraps.  The stream's running sum may (64 jumbo payloads), but
 // a payload's own sum -- at most 32747 words below 2^16 -- is the difference
@@ -49,25 +50,6 @@
 
 namespace wc {
 namespace {
-
-typedef uint32_t __attribute__((address_space(1))) *gst32_ptr;
-typedef uint16_t __attribute__((address_space(1))) *gst16_ptr;
-typedef uint8_t __attribute__((address_space(1))) *gst8_ptr;
-
-struct GlobalMem { // txb::store_headers' stores: global memory, natural alignment
-    __device__ __forceinline__ void st32(uint64_t a, uint32_t v) const
-    {
-        *(gst32_ptr)(uintptr_t)a = v;
-    }
-    __device__ __forceinline__ void st16(uint64_t a, uint32_t v) const
-    {
-        *(gst16_ptr)(uintptr_t)a = (uint16_t)v;
-    }
-    __device__ __forceinline__ void st8(uint64_t a, uint32_t v) const
-    {
-        *(gst8_ptr)(uintptr_t)a = (uint8_t)v;
-    }
-};
 
 // Frame p's offset and descriptor, or frame 0's past the batch end -- with
 // unconditional loads (meta_load's shape).
@@ -196,8 +178,7 @@ hipError_t launch_tx_build(void *base, const uint64_t *offs, const void *desc, u
                            uint8_t *status, uint16_t *out_ip, uint16_t *out_udp, uint64_t *errors,
                            bool nt, hipStream_t st)
 {
-    const uint64_t tiles = (n + 63) / 64;
-    const int grid = (int)std::min<uint64_t>(kMaxGridBlocks, std::max<uint64_t>(1, tiles));
+    const int grid = tile_grid(n);
     const uint32_t zu = (flags & kTxZeroUdp) ? 1u : 0u;
     const bool store = !(flags & kTxNoStore);
 #define WC_TXB(N, S)                                                           \

@@ -413,6 +413,56 @@ inline uint64_t rx_count_drops(const uint8_t *v, uint64_t n)
     return drops;
 }
 
+// --- wc_rt_rxreply.cpp, wc_rt_rxneigh.cpp -------------------------------------
+constexpr uint64_t kRxListMax = 1ull << 32; // a list's indices are uint32
+
+// An empty batch's counts (either may be NULL): device memory, so they are
+// zeroed on the caller's stream.
+inline int rx_zero_counts(uint64_t *a, uint64_t *b, hipStream_t st)
+{
+    if (!a && !b)
+        return WC_OK;
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    hipError_t e = a ? hipMemsetAsync(a, 0, sizeof(uint64_t), st) : hipSuccess;
+    if (e == hipSuccess && b)
+        e = hipMemsetAsync(b, 0, sizeof(uint64_t), st);
+    return hip_err(e);
+}
+
+// A plan call's list scratch: given and 4-byte aligned wherever a list is.
+inline bool rx_scratch_ok(bool lists, const void *d_scratch)
+{
+    return !lists || (d_scratch && !((uintptr_t)d_scratch & 3u));
+}
+
+// wc_rx_reply_build / wc_rx_neigh_build around their one launch: the argument
+// checks in their order (ptrs: every pointer a call with m != 0 and n != 0
+// reads is given, the table 4-byte aligned), *d_built zeroed -- the launch's
+// workgroups, as many as the device holds at once, add to it -- and with no
+// frame every length zeroed instead of a launch.  launch(cus) -> hipError_t.
+template <class Launch>
+int rx_list_build(uint64_t n, uint32_t m, uint32_t slot_bytes, bool ptrs, uint16_t *d_out_len,
+                  uint64_t *d_built, hipStream_t st, Launch launch)
+{
+    if (n > kRxListMax || slot_bytes > 65535u || !d_built)
+        return WC_EINVAL;
+    if (m != 0 && !d_out_len)
+        return WC_EINVAL;
+    if (m != 0 && n != 0 && !ptrs)
+        return WC_EINVAL;
+    Ready R;
+    if (R.rc)
+        return R.rc;
+    hipError_t e = hipMemsetAsync(d_built, 0, sizeof(uint64_t), st);
+    if (e == hipSuccess && m != 0 && n == 0) // no frame, no reply
+        e = hipMemsetAsync(d_out_len, 0, sizeof(uint16_t) * (size_t)m, st);
+    else if (e == hipSuccess && m != 0)
+        e = launch(R.D->cus);
+    return hip_err(e);
+}
+
 // --- wc_rt_server.cpp ---------------------------------------------------------
 constexpr int kSrvFallback = 1; // serve_batch: not served, take the launch path
 // One small registered batch through the server (caller holds g_mu, the

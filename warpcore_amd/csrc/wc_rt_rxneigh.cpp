@@ -21,8 +21,6 @@ static_assert(rn::kMaskReply == ((1u << rn::kArpIsAt) | (1u << rn::kNadv)) &&
                   rn::kMaskUpdate == ((1u << rn::kUpdate4) | (1u << rn::kUpdate6) | rn::kMaskReply),
               "the masks are the codes' bits");
 
-static constexpr uint64_t kRxNeighMax = 1ull << 32; // the lists' indices are uint32
-
 extern "C" {
 
 int wc_rx_neigh_plan(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len,
@@ -32,25 +30,14 @@ int wc_rx_neigh_plan(const void *d_base, const uint64_t *d_off, const uint16_t *
 {
     if ((d_rlist != nullptr) != (d_rcount != nullptr) || (d_ulist != nullptr) != (d_ucount != nullptr))
         return WC_EINVAL;
-    if (n > kRxNeighMax)
+    if (n > kRxListMax)
         return WC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (n == 0) { // an empty batch: zero counts (device memory, so on the caller's stream)
-        if (!d_rcount && !d_ucount)
-            return WC_OK;
-        Ready R;
-        if (R.rc)
-            return R.rc;
-        hipError_t e = hipSuccess;
-        if (d_rcount)
-            e = hipMemsetAsync(d_rcount, 0, sizeof(uint64_t), st);
-        if (e == hipSuccess && d_ucount)
-            e = hipMemsetAsync(d_ucount, 0, sizeof(uint64_t), st);
-        return hip_err(e);
-    }
+    if (n == 0) // an empty batch: zero counts
+        return rx_zero_counts(d_rcount, d_ucount, st);
     if (!d_base || !d_off || !d_frame_len || !d_action || !d_eng || ((uintptr_t)d_eng & 3u) || !d_nact)
         return WC_EINVAL;
-    if ((d_rlist || d_ulist) && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
+    if (!rx_scratch_ok(d_rlist || d_ulist, d_scratch))
         return WC_EINVAL;
     Ready R;
     if (R.rc)
@@ -68,7 +55,7 @@ int wc_rx_neigh_updates(const void *d_base, const uint64_t *d_off, const uint16_
                         const uint64_t *d_count, uint32_t m, struct wc_neigh_update *d_upd,
                         void *stream)
 {
-    if (n > kRxNeighMax)
+    if (n > kRxListMax)
         return WC_EINVAL;
     if (m != 0 && (!d_upd || ((uintptr_t)d_upd & 3u)))
         return WC_EINVAL;
@@ -94,27 +81,13 @@ int wc_rx_neigh_build(const void *d_base, const uint64_t *d_off, const uint16_t 
                       const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
                       uint16_t *d_out_len, uint64_t *d_built, void *stream)
 {
-    if (n > kRxNeighMax || slot_bytes > 65535u || !d_built)
-        return WC_EINVAL;
-    if (m != 0 && !d_out_len)
-        return WC_EINVAL;
-    if (m != 0 && n != 0 &&
-        (!d_base || !d_off || !d_frame_len || !d_nact || !d_list || !d_count || !d_eng ||
-         ((uintptr_t)d_eng & 3u) || !d_out_base || !d_out_off))
-        return WC_EINVAL;
-    Ready R;
-    if (R.rc)
-        return R.rc;
-    // The count of built replies: zeroed here, added to by the launch's
-    // workgroups, as many as the device holds at once.
-    hipError_t e = hipMemsetAsync(d_built, 0, sizeof(uint64_t), (hipStream_t)stream);
-    if (e == hipSuccess && m != 0 && n == 0) // no frame, no reply
-        e = hipMemsetAsync(d_out_len, 0, sizeof(uint16_t) * (size_t)m, (hipStream_t)stream);
-    else if (e == hipSuccess && m != 0)
-        e = wc::launch_rx_neigh_build(d_base, d_off, d_frame_len, n, d_nact, d_list, d_count, d_eng,
-                                      d_out_base, d_out_off, m, slot_bytes, d_out_len, d_built,
-                                      R.D->cus, (hipStream_t)stream);
-    return hip_err(e);
+    const bool ptrs = d_base && d_off && d_frame_len && d_nact && d_list && d_count && d_eng &&
+                      !((uintptr_t)d_eng & 3u) && d_out_base && d_out_off;
+    return rx_list_build(n, m, slot_bytes, ptrs, d_out_len, d_built, (hipStream_t)stream, [&](int cus) {
+        return wc::launch_rx_neigh_build(d_base, d_off, d_frame_len, n, d_nact, d_list, d_count, d_eng,
+                                         d_out_base, d_out_off, m, slot_bytes, d_out_len, d_built,
+                                         cus, (hipStream_t)stream);
+    });
 }
 
 } // extern "C"

@@ -15,8 +15,6 @@ static_assert(WC_RX_MAX_IFADDR == rr::kMaxIfaddr && WC_RR_MASK_REPLY == rr::kMas
                   WC_RR_UNREACH_PROTO4 == rr::kUnreachProto4 && WC_RR_ECHO4 == rr::kEcho4,
               "header and kernels agree");
 
-static constexpr uint64_t kRxReplyMax = 1ull << 32; // the list's indices are uint32
-
 extern "C" {
 
 int wc_rx_engine_check(const struct wc_rx_engine *e)
@@ -41,20 +39,14 @@ int wc_rx_reply_plan(const void *d_base, const uint64_t *d_off, const uint16_t *
                      uint16_t *d_reply_len, uint32_t *d_list, uint64_t *d_count, void *d_scratch,
                      void *stream)
 {
-    if (n > kRxReplyMax || (d_list != nullptr) != (d_count != nullptr))
+    if (n > kRxListMax || (d_list != nullptr) != (d_count != nullptr))
         return WC_EINVAL;
-    if (n == 0) { // an empty batch: a zero count (device memory, so on the caller's stream)
-        if (!d_count)
-            return WC_OK;
-        Ready R;
-        if (R.rc)
-            return R.rc;
-        return hip_err(hipMemsetAsync(d_count, 0, sizeof(uint64_t), (hipStream_t)stream));
-    }
+    if (n == 0) // an empty batch: a zero count
+        return rx_zero_counts(d_count, nullptr, (hipStream_t)stream);
     if (slot_bytes > 65535u || !d_base || !d_off || !d_frame_len || !d_verdict || !d_eng ||
         ((uintptr_t)d_eng & 3u) || !d_action || !d_reply_len)
         return WC_EINVAL;
-    if (d_list && (!d_scratch || ((uintptr_t)d_scratch & 3u)))
+    if (!rx_scratch_ok(d_list != nullptr, d_scratch))
         return WC_EINVAL;
     Ready R;
     if (R.rc)
@@ -74,27 +66,13 @@ int wc_rx_reply_build(const void *d_base, const uint64_t *d_off, const uint16_t 
                       const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
                       const uint16_t *d_ip_id, uint16_t *d_out_len, uint64_t *d_built, void *stream)
 {
-    if (n > kRxReplyMax || slot_bytes > 65535u || !d_built)
-        return WC_EINVAL;
-    if (m != 0 && !d_out_len)
-        return WC_EINVAL;
-    if (m != 0 && n != 0 &&
-        (!d_base || !d_off || !d_frame_len || !d_action || !d_list || !d_count || !d_eng ||
-         ((uintptr_t)d_eng & 3u) || !d_out_base || !d_out_off))
-        return WC_EINVAL;
-    Ready R;
-    if (R.rc)
-        return R.rc;
-    // The count of built replies: zeroed here, added to by the launch's
-    // workgroups, as many as the device holds at once.
-    hipError_t e = hipMemsetAsync(d_built, 0, sizeof(uint64_t), (hipStream_t)stream);
-    if (e == hipSuccess && m != 0 && n == 0) // no frame, no reply
-        e = hipMemsetAsync(d_out_len, 0, sizeof(uint16_t) * (size_t)m, (hipStream_t)stream);
-    else if (e == hipSuccess && m != 0)
-        e = wc::launch_rx_reply_build(d_base, d_off, d_frame_len, n, d_action, d_list, d_count, d_eng,
-                                      d_out_base, d_out_off, m, slot_bytes, d_ip_id, d_out_len,
-                                      d_built, R.D->cus, (hipStream_t)stream);
-    return hip_err(e);
+    const bool ptrs = d_base && d_off && d_frame_len && d_action && d_list && d_count && d_eng &&
+                      !((uintptr_t)d_eng & 3u) && d_out_base && d_out_off;
+    return rx_list_build(n, m, slot_bytes, ptrs, d_out_len, d_built, (hipStream_t)stream, [&](int cus) {
+        return wc::launch_rx_reply_build(d_base, d_off, d_frame_len, n, d_action, d_list, d_count,
+                                         d_eng, d_out_base, d_out_off, m, slot_bytes, d_ip_id,
+                                         d_out_len, d_built, cus, (hipStream_t)stream);
+    });
 }
 
 } // extern "C"

@@ -9,6 +9,8 @@
 //     word and ip_cksum(ip, hl) of the header as loaded -- frame_hdr over
 //     rx_load's five chunks (IPv4 headers of 20..40 bytes), frame_hdr_slow in
 //     two load rounds of its own (any IHL);
+//   * frame bytes 0..55 as dwords out of the same five chunks (rx_words56: the
+//     RX reply and RX neighbour plans, wc_k_rxreply.hip / wc_k_rxneigh.hip);
 //   * the gathered stream of a tile's frames that need the UDP sum (FrameLds,
 //     frame_payload_cksum).
 // The two decision chains themselves (rx_decide, tx_decide) restate different
@@ -78,6 +80,21 @@ __device__ __forceinline__ void rx_load(uint64_t fa, uint32_t flen, bool valid, 
 #pragma unroll
     for (int k = 0; k < 5; ++k)
         c[k] = load_chunk<false>(valid && cf + 16ull * k < fend ? cf + 16ull * k : zero);
+}
+
+// Frame bytes 0..55 as fourteen dwords (A: bytes 0..19, B: 20..39, C: 40..55):
+// three 20-byte windows rotated out of rx_load's five chunks (frame_hdr's way).
+// What the RX reply and RX neighbour plans read of a frame.
+__device__ __forceinline__ void rx_words56(const u32x4 (&c)[5], uint64_t fa, uint32_t (&A)[5],
+                                           uint32_t (&B)[5], uint32_t (&C)[4])
+{
+    const uint32_t sf = (uint32_t)(fa & 15u);
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
+    win_rot(c[0], c[1], c[2], sf, A);
+    const uint32_t o1 = sf + 20u, o2 = sf + 40u;
+    const bool j1 = o1 >= 32u, j2 = o2 >= 48u;
+    win_rot(j1 ? c[2] : c[1], j1 ? c[3] : c[2], j1 ? c[4] : c[3], o1 & 15u, B);
+    win_rot(j2 ? c[3] : c[2], j2 ? c[4] : c[3], j2 ? z4 : c[4], o2 & 15u, C);
 }
 
 // What either kernel's decision chain takes from the frame's headers.

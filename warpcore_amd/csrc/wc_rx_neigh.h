@@ -3,9 +3,10 @@
 // decision chain of wc_rx_neigh_plan over an ARP frame or an ICMPv6 neighbour
 // solicitation / advertisement, the (address, MAC) record neighbor_update
 // receives, the 42 bytes of an ARP is-at and the 86 bytes of a neighbour
-// advertisement as frame-relative dwords, and the stores of those bytes at any
-// 4-byte phase.  Plain C++ (no device builtin), so a host program compiles the
-// same lines.  The engine table, eq16 and frame_dword are wc_rx_reply.h's.
+// advertisement as frame-relative dwords.  Plain C++ (no device builtin), so a
+// host program compiles the same lines.  The engine table, eq16 and frame_dword
+// are wc_rx_reply.h's; the 14-byte shift and the stores of the reply bytes at
+// any 4-byte phase are wc_tx_build.h's (txb::shift14, store_words<N, N>).
 //
 // Reference decisions and stores restated (read, not copied; paths in the
 // reference tree):
@@ -63,7 +64,7 @@ WC_HD uint32_t chain_head(const uint32_t *e, const Look &f)
         bool have4 = false, mine = false;
         const uint32_t na = rr::eng_naddr(e);
         for (uint32_t k = 0; k < na; ++k) {
-            const uint32_t *a = e + 3u + rr::kIfaddrWords * k;
+            const uint32_t *a = rr::eng_entry(e, k);
             if ((a[0] & 0xFFu) == 4u) {
                 have4 = true;
                 mine = mine || f.tpa == a[1];
@@ -98,7 +99,7 @@ WC_HD uint32_t chain_tail(const uint32_t *e, const uint32_t (&tgt)[4])
     bool mine = false;
     const uint32_t na = rr::eng_naddr(e);
     for (uint32_t k = 0; k < na; ++k) {
-        const uint32_t *a = e + 3u + rr::kIfaddrWords * k;
+        const uint32_t *a = rr::eng_entry(e, k);
         mine = mine || ((a[0] & 0xFFu) == 6u && rr::eq16(tgt, a + 1));
     }
     return mine ? kNadv : kNone;
@@ -155,50 +156,6 @@ WC_HD void record_of(const Mem &m, uint64_t fa, uint32_t flen, uint32_t code, ui
     u[1] = (m0 >> 16) | (m1 << 16);
 }
 
-// The stores of N dwords' first 4 N - 2 bytes (42 for N = 11, 86 for N = 22) at
-// address fa: txb::store_headers' way for any N -- the bytes are shifted to
-// fa's 4-byte phase and written as aligned dwords, the ends as byte / 2-byte
-// stores at their natural alignment, so no byte outside [fa, fa + 4 N - 2) is
-// written at any phase.  Aligned dword j lies at b + 4 j and holds frame bytes
-// [4 j - p, + 4); each is a value computed where it is stored, every index a
-// constant (a select between array elements would put h in scratch).
-// Mem: st8 / st16 / st32(address, value).
-template <int N, class Mem>
-WC_HD void store_words(const Mem &m, uint64_t fa, const uint32_t (&h)[N])
-{
-    const uint32_t p = (uint32_t)(fa & 3u), sh = 8u * p;
-    const uint64_t b = fa - p;
-    const uint32_t rs = (32u - sh) & 31u, keep = p ? 0xFFFFFFFFu : 0u;
-    // the first dword: whole at phase 0, else its upper 4 - p bytes
-    if (p == 0u) {
-        m.st32(b, h[0]);
-    } else if (p == 2u) {
-        m.st16(fa, h[0] & 0xFFFFu);
-    } else {
-        m.st8(fa, h[0] & 0xFFu);
-        if (p == 1u)
-            m.st16(fa + 1u, (h[0] >> 8) & 0xFFFFu);
-    }
-    // whole dwords: 1 .. N - 2 always, N - 1 from phase 2 on (p + 4 N - 2 >= 4 N)
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int j = 1; j < N - 1; ++j)
-        m.st32(b + 4u * j, (h[j] << sh) | ((h[j - 1] >> rs) & keep));
-    const uint32_t last = (h[N - 1] << sh) | ((h[N - 2] >> rs) & keep);
-    const uint64_t ta = b + 4u * (N - 1);
-    if (p >= 2u)
-        m.st32(ta, last);
-    // the tail: 2 bytes at phase 0, 3 at phase 1, none at 2, the last one at 3
-    if (p <= 1u) {
-        m.st16(ta, last & 0xFFFFu);
-        if (p == 1u)
-            m.st8(ta + 2u, (last >> 16) & 0xFFu);
-    } else if (p == 3u) {
-        m.st8(ta + 4u, (h[N - 1] >> 8) & 0xFFu);
-    }
-}
-
 // The reply of `code` to the request at fa, written at da: its length, or 0
 // with nothing written where the code is no reply code, the frame is shorter
 // than the bytes the reply reads (42 / 78) or slot_bytes is below 42 / 86.
@@ -231,7 +188,7 @@ WC_HD uint32_t build(const Mem &m, uint64_t fa, uint32_t flen, uint32_t code, co
         h[8] = s0;
         h[9] = s1 | (spa << 16);
         h[10] = spa >> 16;
-        store_words<11>(m, da, h);
+        txb::store_words<11, 11>(m, da, true, h);
         return kArpLen;
     }
     if (code != kNadv || flen < kTargetEnd || slot_bytes < kNadvLen)
@@ -241,7 +198,7 @@ WC_HD uint32_t build(const Mem &m, uint64_t fa, uint32_t flen, uint32_t code, co
     // destination is always the request's source MAC.
     const uint32_t d0 = rr::frame_dword(m, fa, fend, 6u);
     const uint32_t d1 = rr::frame_dword(m, fa, fend, 10u) & 0xFFFFu;
-    const uint32_t *s = e + 3u + 1u; // entry 0's address (ip6.c:155)
+    const uint32_t *s = rr::eng_entry(e, 0u) + 1; // entry 0's address (ip6.c:155)
     uint32_t ip[18];
     ip[0] = 0x60u; // the whole word, as the existing replies write it
     ip[1] = 0x2000u | (58u << 16) | (0xFFu << 24); // len 00 20, next header, hop limit
@@ -268,14 +225,8 @@ WC_HD uint32_t build(const Mem &m, uint64_t fa, uint32_t flen, uint32_t code, co
     h[0] = d0;
     h[1] = d1 | (mac0 << 16);
     h[2] = macw;
-    h[3] = 0xDD86u | (ip[0] << 16);
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int k = 1; k < 18; ++k)
-        h[3 + k] = (ip[k - 1] >> 16) | (ip[k] << 16);
-    h[21] = ip[17] >> 16;
-    store_words<22>(m, da, h);
+    txb::shift14(0xDD86u, ip, h);
+    txb::store_words<22, 22>(m, da, true, h);
     return kNadvLen;
 }
 

@@ -5,8 +5,9 @@
 // build derives again), the 42 or 62 header bytes of a reply as frame-relative
 // dwords, and the gather-copy of a reply's data with its sum, one aligned
 // destination chunk or dword at a time.  Plain C++ (no device builtin), so a
-// host program compiles the same lines.  The header stores are the TX build's
-// (txb::store_headers).
+// host program compiles the same lines.  The byte swap, the folds, the 14-byte
+// shift and the header stores are the TX build's (txb::bswap16, fold16,
+// shift14, store_headers).
 //
 // Reference decisions and stores restated (read, not copied):
 //   eth_rx     /root/reference/lib/src/eth.c:65-73      MAC filter
@@ -43,6 +44,8 @@ constexpr uint32_t kSockUnbound = 0xFFu;
 // a[1..4] = addr, a[5..8] = bcast, a[9..12] = snma.
 constexpr uint32_t kMaxIfaddr = 16, kIfaddrWords = 13, kEngineWords = 3 + kMaxIfaddr * kIfaddrWords;
 
+using txb::fold16; // rr::fold16: the fold of a reply's data sum (headers' `data`)
+
 WC_HD bool is_reply(uint32_t a)
 {
     return a < 32u && ((kMaskReply >> a) & 1u);
@@ -62,6 +65,12 @@ WC_HD uint32_t eng_mtu(const uint32_t *e)
 WC_HD uint32_t eng_naddr(const uint32_t *e)
 {
     return e[2] < kMaxIfaddr ? e[2] : kMaxIfaddr;
+}
+
+// Address entry k: a[0] = af, a[1..4] = addr, a[5..8] = bcast, a[9..12] = snma.
+WC_HD const uint32_t *eng_entry(const uint32_t *e, uint32_t k)
+{
+    return e + 3u + kIfaddrWords * k;
 }
 
 // eth.c:65-67 on frame bytes 0..3 (d0) and 4..7 (d1): ours, broadcast, or
@@ -91,7 +100,7 @@ WC_HD Match addr_match(const uint32_t *e, bool v4, const uint32_t (&d)[4], const
     bool d4 = false, s4 = false, d6 = false, s6 = false;
     const uint32_t na = eng_naddr(e);
     for (uint32_t k = 0; k < na; ++k) {
-        const uint32_t *a = e + 3u + kIfaddrWords * k;
+        const uint32_t *a = eng_entry(e, k);
         const uint32_t af = a[0] & 0xFFu;
         if (af == 4u) {
             d4 = d4 || d[0] == a[1] || d[0] == a[5] || d[0] == 0xFFFFFFFFu;
@@ -111,7 +120,7 @@ WC_HD uint32_t eng_src4(const uint32_t *e)
     uint32_t src = 0u;
     bool found = false;
     for (uint32_t k = 0; k < na; ++k) {
-        const uint32_t *a = e + 3u + kIfaddrWords * k;
+        const uint32_t *a = eng_entry(e, k);
         if (!found && (a[0] & 0xFFu) == 4u) {
             src = a[1];
             found = true;
@@ -290,8 +299,10 @@ WC_HD Req request_of(const Mem &m, uint64_t fa, uint64_t fend, uint32_t action, 
 
 // The 42 (IPv4) or 62 (IPv6) header bytes of a reply as little-endian dwords
 // from its first byte (the layout of txb::Hdr::h, stored by
-// txb::store_headers).  data = the sum of the data's little-endian words from
-// its first byte on, folded to 16 bits (copy_dword).
+// txb::store_headers).  data = the sum of the data's little-endian words
+// from its first byte on -- copy_dword's and copy_chunk's shares summed (below
+// 2^32 for any dlen <= 65535 across a wave: 32768 words) and folded to 16 bits
+// (rr::fold16 = txb::fold16).
 //
 // No sum wraps.  ip_cksum of the IPv4 header: ten words.  The ICMP sum
 // (icmp4.c:111): four header words and one folded data word, below 2^19.  The
@@ -327,7 +338,7 @@ WC_HD void headers(const Reply &r, const Req &q, const uint32_t *e, uint32_t ip_
         ip[5] = tc | (ck << 16), ip[6] = q.rest;
         ip[7] = ip[8] = ip[9] = ip[10] = ip[11] = 0u;
     } else {
-        const uint32_t *s = e + 3u + 1u;             // entry 0's address (ip6.c:155)
+        const uint32_t *s = eng_entry(e, 0u) + 1;     // entry 0's address (ip6.c:155)
         const uint32_t plen = bswap16(r.len - 54u);   // ip6->len as stored
         uint32_t S = (58u << 24) + plen + words(tc) + words(q.rest) + data;
 #if defined(__clang__)
@@ -349,13 +360,7 @@ WC_HD void headers(const Reply &r, const Req &q, const uint32_t *e, uint32_t ip_
     h[0] = q.smac0;
     h[1] = q.smac1 | (e[0] << 16);
     h[2] = (e[0] >> 16) | (e[1] << 16);
-    h[3] = (v4 ? 0x0008u : 0xDD86u) | (ip[0] << 16);
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int k = 1; k < 12; ++k)
-        h[3 + k] = (ip[k - 1] >> 16) | (ip[k] << 16);
-    h[15] = ip[11] >> 16;
+    txb::shift14(v4 ? 0x0008u : 0xDD86u, ip, h);
 }
 
 // The aligned dwords a reply's data [dd, dd + dlen) touches.
@@ -480,15 +485,6 @@ WC_HD uint32_t copy_chunk(const Mem &m, uint64_t sa, uint64_t dd, uint32_t c)
         o.w = ((o.w & 0x00FF00FFu) << 8) | ((o.w >> 8) & 0x00FF00FFu);
     }
     return txb::words(o.x) + txb::words(o.y) + txb::words(o.z) + txb::words(o.w);
-}
-
-// copy_dword's and copy_chunk's shares summed (below 2^32 for any dlen <=
-// 65535 across a wave: 32768 words) and folded to the one word headers() takes.
-WC_HD uint32_t fold16(uint32_t s)
-{
-    s = (s & 0xFFFFu) + (s >> 16);
-    s = (s & 0xFFFFu) + (s >> 16);
-    return s;
 }
 
 } // namespace rr

@@ -2,8 +2,10 @@
 // call (wc_tx_build_host, wc_rt_tx.cpp) share about one frame, each stated
 // once: the table entries as little-endian dwords, the
 // check chain, the 42 or 62 header bytes as frame-relative dwords, and the
-// stores of those bytes at any 4-byte phase.  Plain C++ (no device builtin),
-// so the host call and a host test compile the same lines.
+// stores of those bytes at any 4-byte phase.  The RX reply and RX neighbour
+// paths (wc_rx_reply.h, wc_rx_neigh.h) take the byte swap, the folds, the
+// 14-byte shift (shift14) and the stores (store_words) from here.  Plain C++
+// (no device builtin), so the host call and a host test compile the same lines.
 //
 // Reference stores restated (read, not copied):
 //   mk_eth_hdr  /root/reference/lib/src/eth.h:89-109    dst, src, type
@@ -57,12 +59,32 @@ WC_HD uint32_t words(uint32_t x)
     return (x & 0xFFFFu) + (x >> 16);
 }
 
-// in_cksum.c:74-80 on a sum below 2^32.
-WC_HD uint32_t fold_not16(uint32_t s)
+// A sum below 2^32 folded to 16 bits, and in_cksum.c:74-80 on it.
+WC_HD uint32_t fold16(uint32_t s)
 {
     s = (s & 0xFFFFu) + (s >> 16);
     s = (s & 0xFFFFu) + (s >> 16);
-    return ~s & 0xFFFFu;
+    return s;
+}
+
+WC_HD uint32_t fold_not16(uint32_t s)
+{
+    return ~fold16(s) & 0xFFFFu;
+}
+
+// N dwords that follow an Ethernet header, as frame-relative dwords: they lie
+// 14 bytes into the frame, behind dst, src (h[0 .. 2], the caller's) and the
+// EtherType as stored.  h[3 + N] holds the last two bytes in its low half.
+template <int N>
+WC_HD void shift14(uint32_t etype, const uint32_t (&ip)[N], uint32_t (&h)[N + 4])
+{
+    h[3] = etype | (ip[0] << 16);
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int k = 1; k < N; ++k)
+        h[3 + k] = (ip[k - 1] >> 16) | (ip[k] << 16);
+    h[3 + N] = ip[N - 1] >> 16;
 }
 
 // The check chain (wc_cksum.h, "TX build"), in its order.  sock_in / dst_in:
@@ -163,31 +185,31 @@ WC_HD Hdr headers(const Decide &x, const Desc &d, const uint32_t (&w)[kSockWords
     r.h[0] = dm0;
     r.h[1] = dm1 | (w[1] & 0xFFFF0000u);
     r.h[2] = w[2];
-    r.h[3] = (v4 ? 0x0008u : 0xDD86u) | (ip[0] << 16);
-#if defined(__clang__)
-#pragma unroll
-#endif
-    for (int k = 1; k < 12; ++k)
-        r.h[3 + k] = (ip[k - 1] >> 16) | (ip[k] << 16);
-    r.h[15] = ip[11] >> 16;
+    shift14(v4 ? 0x0008u : 0xDD86u, ip, r.h);
     return r;
 }
 
-// The stores of a frame's hb = 42 or 62 header bytes at address fa (a
-// byte-granular integer): the bytes are shifted to fa's 4-byte phase and
-// written as aligned dwords, the ends as byte / 2-byte stores at their natural
-// alignment, so no byte outside [fa, fa + hb) is written at any phase.  Mem:
-// st8 / st16 / st32(address, value).  hb is 2 mod 4, which fixes the shape of
-// the two ends per phase.
-template <class Mem>
-WC_HD void store_headers(const Mem &m, uint64_t fa, bool v4, const uint32_t (&h)[16])
+// The stores of h's first 4 N - 2 bytes at address fa (a byte-granular
+// integer), N = NA where short_form holds and NB otherwise -- 42 or 62 header
+// bytes for <11, 16>, a fixed length where NA == NB (the choice then folds at
+// compile time): the bytes are shifted to fa's 4-byte phase and written as
+// aligned dwords, the ends as byte / 2-byte stores at their natural alignment,
+// so no byte outside [fa, fa + 4 N - 2) is written at any phase.  Mem: st8 /
+// st16 / st32(address, value).  The length is 2 mod 4, which fixes the shape
+// of the two ends per phase.  One statement for both lengths, not one call per
+// length: the lanes of a TX build tile differ in short_form, and two calls
+// would run one after the other in a mixed tile.
+template <int NA, int NB, class Mem>
+WC_HD void store_words(const Mem &m, uint64_t fa, bool short_form, const uint32_t (&h)[NB])
 {
+    static_assert(2 <= NA && NA <= NB, "the short form is a prefix of the long one");
+    const bool sf = NA == NB || short_form;
     const uint32_t p = (uint32_t)(fa & 3u), sh = 8u * p;
     const uint64_t b = fa - p; // aligned dword j lies at b + 4 j and holds frame bytes [4 j - p, + 4)
-    // Aligned dword j, 1 <= j <= 15, computed where it is stored: values, not
-    // elements of a shifted array (a select between two array elements becomes
-    // a dynamic index, and a 64-bit funnel of two neighbours one 8-byte load of
-    // the array: either puts it in scratch).
+    // Aligned dword j, 1 <= j < NB, computed where it is stored: values, not
+    // elements of a shifted array, and every index a constant (a select between
+    // two array elements becomes a dynamic index, and a 64-bit funnel of two
+    // neighbours one 8-byte load of the array: either puts h in scratch).
     const uint32_t rs = (32u - sh) & 31u, keep = p ? 0xFFFFFFFFu : 0u;
     auto al = [&](int j) { return (h[j] << sh) | ((h[j - 1] >> rs) & keep); };
     // the first dword: whole at phase 0, else its upper 4 - p bytes
@@ -200,33 +222,34 @@ WC_HD void store_headers(const Mem &m, uint64_t fa, bool v4, const uint32_t (&h)
         if (p == 1u)
             m.st16(fa + 1u, (h[0] >> 8) & 0xFFFFu);
     }
-    // whole dwords: 1 .. 9 always; 10 from phase 2 on or for IPv6; 11 .. 14 for
-    // IPv6; 15 for IPv6 from phase 2 on (p + 62 >= 64)
+    // whole dwords: 1 .. NA - 2 always; NA - 1 from phase 2 on (p + 4 NA - 2 >=
+    // 4 NA) or for the long form; NA .. NB - 2 for the long form; NB - 1 for the
+    // long form from phase 2 on
 #if defined(__clang__)
 #pragma unroll
 #endif
-    for (int j = 1; j < 10; ++j)
+    for (int j = 1; j < NA - 1; ++j)
         m.st32(b + 4u * j, al(j));
-    const uint32_t a10 = al(10), a15 = al(15);
-    if (!v4 || p >= 2u)
-        m.st32(b + 40u, a10);
-    if (!v4) {
+    const uint32_t aa = al(NA - 1), ab = al(NB - 1);
+    if (!sf || p >= 2u)
+        m.st32(b + 4u * (NA - 1), aa);
+    if (!sf) {
 #if defined(__clang__)
 #pragma unroll
 #endif
-        for (int j = 11; j < 15; ++j)
+        for (int j = NA; j < NB - 1; ++j)
             m.st32(b + 4u * j, al(j));
         if (p >= 2u)
-            m.st32(b + 60u, a15);
+            m.st32(b + 4u * (NB - 1), ab);
     }
-    // the last dword's first (p + 2) & 3 bytes: dword (p + hb) >> 2, of which
-    // only phases 0, 1 (dword 10 / 15) and 3 (dword 11 / 16: the frame's last
-    // byte) have any
-    const uint32_t m4 = v4 ? 0xFFFFFFFFu : 0u;
-    const uint32_t hi = (h[10] & m4) | (h[15] & ~m4); // the headers' last two bytes (no select
-                                                      // between elements: see above)
-    const uint32_t tl = p >= 2u ? (hi >> 8) & 0xFFu : (v4 ? a10 : a15);
-    const uint32_t je = (v4 ? 10u : 15u) + (p >= 2u ? 1u : 0u);
+    // the last dword's first (p + 2) & 3 bytes: dword (p + 4 N - 2) >> 2, of
+    // which only phases 0, 1 (dword N - 1) and 3 (dword N: the last byte) have
+    // any
+    const uint32_t m4 = sf ? 0xFFFFFFFFu : 0u;
+    const uint32_t hi = (h[NA - 1] & m4) | (h[NB - 1] & ~m4); // the last two bytes (no select
+                                                              // between elements: see above)
+    const uint32_t tl = p >= 2u ? (hi >> 8) & 0xFFu : (sf ? aa : ab);
+    const uint32_t je = (sf ? NA - 1u : NB - 1u) + (p >= 2u ? 1u : 0u);
     const uint64_t ta = b + 4u * je;
     if (p == 0u) {
         m.st16(ta, tl & 0xFFFFu);
@@ -236,6 +259,13 @@ WC_HD void store_headers(const Mem &m, uint64_t fa, bool v4, const uint32_t (&h)
     } else if (p == 3u) {
         m.st8(ta, tl & 0xFFu);
     }
+}
+
+// The 42 (v4) or 62 header bytes of Hdr::h, a built frame's or a reply's.
+template <class Mem>
+WC_HD void store_headers(const Mem &m, uint64_t fa, bool v4, const uint32_t (&h)[16])
+{
+    store_words<11, 16>(m, fa, v4, h);
 }
 
 } // namespace txb
