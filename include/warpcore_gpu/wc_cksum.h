@@ -611,8 +611,9 @@ int wc_rx_reply_build(const void *d_base, const uint64_t *d_off, const uint16_t 
  * (icmp6.c:270-322) with the advertisement icmp6_tx writes (icmp6.c:168-193,
  * 221-228).  All of it is a function of the frame bytes and the engine table;
  * the host applies the (address, MAC) records to its cache in order
- * (neighbor_update) and posts the built frames.  The cache itself, the who_has
- * loop and its solicitations stay the host's. */
+ * (neighbor_update) and posts the built frames -- or hands the records to
+ * wc_neigh_apply ("TX neighbours" below), which keeps the cache, the who_has
+ * lookup and its solicitations on the device. */
 enum wc_rx_neigh_action {        /* uint8, all < 32 so wc_rx_select masks apply */
     WC_RN_NONE = 0,              /* nothing to do */
     WC_RN_MALFORMED = 4,         /* a byte the reference would read lies past the frame */
@@ -724,6 +725,157 @@ int wc_rx_neigh_build(const void *d_base, const uint64_t *d_off, const uint16_t 
                       const struct wc_rx_engine *d_eng,
                       void *d_out_base, const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
                       uint16_t *d_out_len, uint64_t *d_built, void *stream);
+
+/* --- TX neighbours: device neighbour cache, batched who_has, solicitations - */
+
+/* What lies between "RX produces update records" and "TX consumes destination
+ * MACs" in the reference: the hash table of neighbor.c (neighbor_update,
+ * neighbor.c:48-65; neighbor_find, 75-82), the who_has loop (95-118) and the two
+ * frames it sends, arp_who_has (arp.c:107-142) and icmp6_nsol (icmp6.c:85-129).
+ * A ring's ARP replies reach the next TX batch's Ethernet headers without the
+ * host touching an address.  What stays the host's: blocking on the answer
+ * (the caller holds the HELD frames for a later round), the spare buffers, the
+ * TX ring.
+ *
+ * The cache is an opaque device table of wc_neigh_tab_bytes(cap) = 64 + 32 cap
+ * bytes (a 64-byte header, 32-byte entries), 16-byte aligned: open-addressed,
+ * of fixed capacity, and it never deletes (the reference never does, short of
+ * free_neighbor); a second wc_neigh_tab_init is the flush.  cap is a power of
+ * two in [64, 2^20]; any other cap is WC_EINVAL, or 0 bytes.  Sizing the table
+ * so that it stays at most half full is the caller's job.
+ * Ordering: calls that use one table (init, apply, resolve) are ordered by the
+ * caller -- the same stream, or events; an apply and a resolve of one table must
+ * not run at once. */
+#define WC_NEIGH_TAB_MIN_CAP 64u
+#define WC_NEIGH_TAB_MAX_CAP (1u << 20)
+uint64_t wc_neigh_tab_bytes(uint32_t cap);                       /* 0 for a bad cap */
+/* Asynchronous on `stream`, one launch.  WC_EINVAL: a bad cap, a NULL or not
+ * 16-byte-aligned d_tab. */
+int wc_neigh_tab_init(void *d_tab, uint32_t cap, void *stream);
+
+/* neighbor_update for the records j < MIN(*d_count, m) of a wc_rx_neigh_updates
+ * array, applied as if in order: afterwards every address a record names maps
+ * to the MAC of the last record that names it, and every address that was in
+ * the table and is not named keeps its MAC.  Records with af 0 (the empty ones)
+ * are skipped; an af other than 0 / 4 / 6 is skipped and counted in *d_dropped.
+ * The key is (af, addr); for af 4 only addr bytes 0..3 count, and af 4 a.b.c.d
+ * and af 6 a.b.c.d:: are different keys.  A record whose key is neither present
+ * nor insertable (the table is full) is dropped and counted: the keys present
+ * afterwards are the old ones plus MIN(free entries, new distinct keys) of the
+ * new ones -- which of them is unspecified --, every key present has the MAC of
+ * its last record, and *d_dropped (device uint64, optional, accumulated) counts
+ * the records whose key is not present.
+ * The result, read through lookups, is the same for the same input however the
+ * lanes interleave (but for which new keys a full table keeps); no lane waits for another's store (no spin, no lock), every
+ * loop is bounded by cap; two launches, asynchronous on `stream`; atomics only
+ * on the table's own words and on *d_dropped (one per workgroup).  d_scratch:
+ * wc_neigh_apply_scratch(m) = 4 m bytes of device memory, the caller's, one per
+ * call in flight.  cap is read from the table's header on the device; a table
+ * that was never initialised is the caller's error (the device then applies
+ * nothing and counts every record as dropped, where it can tell).
+ * m = 0 is WC_OK and looks at no pointer.  WC_EINVAL, before a device is
+ * touched: with m > 0 a NULL d_tab / d_upd / d_count / d_scratch, d_tab not
+ * 16-byte or d_upd / d_scratch not 4-byte aligned, m > 2^31. */
+uint64_t wc_neigh_apply_scratch(uint32_t m);
+int wc_neigh_apply(void *d_tab, const struct wc_neigh_update *d_upd, const uint64_t *d_count,
+                   uint32_t m, uint64_t *d_dropped, void *d_scratch, void *stream);
+
+/* Pure host arithmetic over a host copy of the table (no GPU, no library
+ * state), like wc_rx_socktab_lookup: the same hash and probe the device runs.
+ * Lookup: 1 and mac written for a hit, 0 for a miss; WC_EINVAL for a NULL or not
+ * 4-byte-aligned h_tab, bytes wc_neigh_tab_init did not write, a NULL addr /
+ * mac, an af other than 4 / 6 (af 4: 4 address bytes are read).  Stats: the
+ * capacity and the number of entries in use (either pointer may be NULL). */
+int wc_neigh_tab_lookup(const void *h_tab, uint8_t af, const uint8_t *addr, uint8_t mac[6]);
+int wc_neigh_tab_stats(const void *h_tab, uint32_t *cap, uint32_t *used);
+
+/* The batched who_has over a destination table.  struct wc_tx_dst has no family
+ * field, so d_af[k] (4 or 6) says how d_dsts[k].addr is read.  Per entry k <
+ * ndst, d_state[k] is:
+ *   READY     neighbor_find (neighbor.c:75-82) gave a MAC that is not
+ *             ff:ff:ff:ff:ff:ff: it is written to d_dsts[k].dmac.
+ *   BAD_AF    d_af[k] is not 4 / 6: the entry is untouched.
+ *   MISS / MISS_DUP   no entry, or a cached broadcast MAC (who_has treats it as
+ *             unresolved, neighbor.c:102): dmac is written ff x 6, what
+ *             neighbor_find returns; MISS for the lowest index k with that (af,
+ *             address) among the array's misses, MISS_DUP for the others -- one
+ *             solicitation per distinct unresolved address, the batch form of
+ *             the reference's blocking loop, in which a second send to the same
+ *             address finds it resolved.
+ * addr, port and every byte outside dmac are never written.  With d_list /
+ * d_count (both or neither): wc_rx_select(d_state, ndst, WC_NR_MASK_SOLICIT,
+ * ...) behind it, ascending.  The de-duplication has wc_neigh_apply's contract:
+ * "lowest index wins" whatever the interleaving, no waiting, bounded loops,
+ * atomics only on d_scratch's words.  d_scratch: wc_tx_resolve_scratch(ndst)
+ * bytes (0 for ndst = 0 or > 65536), 4-byte aligned, needed with or without a
+ * list.  ndst = 0 is WC_OK and writes a 0 count if one is given.  WC_EINVAL: a
+ * list without its count or a count without its list, ndst > 65536 (the
+ * build's limit), a NULL d_tab / d_dsts / d_af / d_state / d_scratch, d_tab not
+ * 16-byte or d_dsts / d_scratch not 4-byte aligned.  Asynchronous on `stream`:
+ * a memset and two launches, three more with the list. */
+enum wc_neigh_resolve {          /* uint8, all < 32 so wc_rx_select masks apply */
+    WC_NR_READY = 0,             /* in the cache: dmac written */
+    WC_NR_BAD_AF = 4,            /* d_af[k] is not 4 / 6: entry untouched */
+    WC_NR_MISS = 8,              /* not in the cache, first entry of the array with this address: solicit */
+    WC_NR_MISS_DUP = 9,          /* not in the cache, an earlier entry has the same (af, address) */
+};
+#define WC_NR_MASK_SOLICIT (0x100u)
+#define WC_NR_MASK_MISS    (0x300u)
+uint64_t wc_tx_resolve_scratch(uint32_t ndst);
+int wc_tx_resolve(const void *d_tab, struct wc_tx_dst *d_dsts, const uint8_t *d_af, uint32_t ndst,
+                  uint8_t *d_state, uint32_t *d_list, uint64_t *d_count, void *d_scratch, void *stream);
+
+/* What the host would otherwise work out per frame from d_state: d_hold[i] by
+ * this chain over frame i's descriptor, first hit wins.
+ *   1. sock >= ns, or the socket's af is not 4 / 6:     MALFORMED (the build's check 1).
+ *   2. a connected socket:                              READY.
+ *   3. dst >= ndst, or d_af[dst] is not the socket's af: MALFORMED.
+ *   4. d_state[dst] == WC_NR_READY:                     READY.
+ *   5. otherwise:                                       HELD.
+ * With d_list / d_count (both or neither): wc_rx_select(d_hold, n,
+ * WC_TH_MASK_HELD, ...), d_scratch of wc_rx_select_scratch(n) bytes.  The
+ * caller passes the READY frames to wc_tx_build_ragged and keeps the HELD ones
+ * for the next round.  n = 0 is WC_OK and writes a 0 count if one is given.
+ * WC_EINVAL: a list without its count or the reverse, n > 2^32, ns > 256, ndst
+ * > 65536, a NULL or not 8-byte-aligned d_desc, a NULL d_hold, NULL or not
+ * 4-byte-aligned d_socks with ns > 0, NULL d_state / d_af with ndst > 0, a list
+ * without a 4-byte-aligned d_scratch.  One launch, three more with the list;
+ * no atomic. */
+enum wc_tx_hold { WC_TH_READY = 0, WC_TH_MALFORMED = 4, WC_TH_HELD = 8 };
+#define WC_TH_MASK_HELD (0x100u)
+int wc_tx_hold_plan(const struct wc_tx_desc *d_desc, uint64_t n, const struct wc_tx_sock *d_socks, uint32_t ns,
+                    const uint8_t *d_state, const uint8_t *d_af, uint32_t ndst,
+                    uint8_t *d_hold, uint32_t *d_list, uint64_t *d_count, void *d_scratch, void *stream);
+
+/* The contract of wc_rx_neigh_build for wc_tx_resolve's d_list / d_count: frame
+ * j < MIN(*d_count, m) solicits d_dsts[d_list[j]], is written at d_out_base +
+ * d_out_off[j] and d_out_len[j] is its length; *d_built is written, not
+ * accumulated.  d_out_len[j] is 0 and the slot untouched where the index is >=
+ * ndst, d_af is not 4 / 6, slot_bytes is below 42 / 86, j is at or past the
+ * count, or the engine table has no entry of that family (no af-4 entry; entry
+ * 0 not af 6) -- a deliberate difference: the reference would read an unset
+ * ifaddr[addr4_pos] / ifaddr[0] there.  Nothing outside [slot, slot + length)
+ * is written; all stores are plain vector stores.
+ *   ARP who-has, 42 bytes (arp.c:107-142): dst ff x 6, src = mac, 08 06; 00 01
+ *     08 00 06 04 00 01; sha = mac, spa = the first af-4 entry's address, tha =
+ *     00 x 6, tpa = addr[0..3].
+ *   Neighbour solicitation, 86 bytes (icmp6.c:85-129, 60-78; ip6.c:127-161;
+ *     ip6.h:61-67, 154-158): dst 33 33 then target bytes 12..15 (the
+ *     reference's form, not RFC 2464's 33 33 ff), src = mac, 86 dd; 60 00 00 00
+ *     (written whole, as the existing replies), 00 20, 3a, ff, src = entry 0's
+ *     address, dst = ff 02 00 .. 00 01 ff then target bytes 13..15; 87 00,
+ *     checksum, 60 00 00 00 (the reference sets id = 0x60 on a solicitation
+ *     too; the quirk is kept), the 16 target bytes, 01 01, mac.  Checksum:
+ *     payload_cksum(ip, 72) with the field taken as 0, stored raw.
+ * m = 0 is WC_OK, writes *d_built = 0 and looks at no other pointer; ndst = 0
+ * writes that and m zero lengths.  WC_EINVAL: as wc_rx_neigh_build (ndst in
+ * the place of n, at most 65536; d_dsts and d_eng 4-byte aligned).  The only
+ * atomic is the built count's, one per workgroup of a grid no larger than the
+ * device holds at once. */
+int wc_tx_solicit_build(const struct wc_tx_dst *d_dsts, const uint8_t *d_af, uint32_t ndst,
+                        const uint32_t *d_list, const uint64_t *d_count, const struct wc_rx_engine *d_eng,
+                        void *d_out_base, const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
+                        uint16_t *d_out_len, uint64_t *d_built, void *stream);
 
 /* --- host-memory batch (end-to-end: pinned H2D, kernel, D2H) ------------- */
 

@@ -55,6 +55,17 @@ SIGNATURES = {
     "wc_rx_neigh_updates": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
     "wc_rx_neigh_build": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
                                  _vp, _vp, _vp]),
+    "wc_neigh_tab_bytes": (_u64, [_u32]),
+    "wc_neigh_tab_init": (_int, [_vp, _u32, _vp]),
+    "wc_neigh_apply_scratch": (_u64, [_u32]),
+    "wc_neigh_apply": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "wc_neigh_tab_lookup": (_int, [_vp, ctypes.c_uint8, _vp, _vp]),
+    "wc_neigh_tab_stats": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "wc_tx_resolve_scratch": (_u64, [_u32]),
+    "wc_tx_resolve": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "wc_tx_hold_plan": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "wc_tx_solicit_build": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp,
+                                   _vp]),
     "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "wc_tx_socks_check": (_int, [_vp, _u32]),

@@ -1065,6 +1065,218 @@ def tx_build_ragged(base: torch.Tensor, offsets: torch.Tensor, descs: torch.Tens
     return frame_len, status, hdr, udp, errors
 
 
+# --------------------------------------------------------------------------
+# TX neighbours (neighbor.c's cache on the device, who_has for a whole
+# destination table, arp_who_has / icmp6_nsol frames).
+
+NEIGH_TAB_MIN_CAP, NEIGH_TAB_MAX_CAP = 64, 1 << 20
+# enum wc_neigh_resolve, enum wc_tx_hold
+NR_READY, NR_BAD_AF, NR_MISS, NR_MISS_DUP = 0, 4, 8, 9
+NR_MASK_SOLICIT, NR_MASK_MISS = 0x100, 0x300
+NR_NAMES = {NR_READY: "ready", NR_BAD_AF: "bad_af", NR_MISS: "miss", NR_MISS_DUP: "miss_dup"}
+TH_READY, TH_MALFORMED, TH_HELD = 0, 4, 8
+TH_MASK_HELD = 0x100
+TH_NAMES = {TH_READY: "ready", TH_MALFORMED: "malformed", TH_HELD: "held"}
+_NEIGH_APPLY_MAX = 1 << 31
+
+
+def neigh_tab_bytes(cap: int) -> int:
+    """Bytes of a neighbour table of ``cap`` entries (wc_neigh_tab_bytes, no
+    GPU).  ``ValueError`` unless cap is a power of two in [64, 2^20]."""
+    cap = int(cap)
+    nb = int(_lib.active().wc_neigh_tab_bytes(cap)) if 0 <= cap <= 0xFFFFFFFF else 0
+    if nb == 0:
+        raise ValueError(f"cap must be a power of two in [{NEIGH_TAB_MIN_CAP}, {NEIGH_TAB_MAX_CAP}]")
+    return nb
+
+
+def _neigh_tab(tab: torch.Tensor) -> None:
+    if not isinstance(tab, torch.Tensor) or not tab.is_cuda or not tab.is_contiguous() \
+            or tab.data_ptr() % 16 or _nbytes(tab) < 64 + 32 * NEIGH_TAB_MIN_CAP:
+        raise ValueError("tab must be the contiguous, 16-byte aligned device tensor neigh_tab_init gave")
+
+
+def neigh_tab_init(cap: int, device=None, stream=None,
+                   tab: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """An empty neighbour table of ``cap`` entries on ``device``
+    (wc_neigh_tab_init): a uint8 device tensor of ``neigh_tab_bytes(cap)``
+    bytes, allocated here unless ``tab`` -- an earlier one of at least that size
+    -- is given; initialising a table again is the flush.  Asynchronous."""
+    nb = neigh_tab_bytes(cap)
+    if tab is None:
+        if device is None:
+            raise ValueError("neigh_tab_init needs a device or a tab")
+        tab = torch.empty(nb, dtype=torch.uint8, device=device)
+    _neigh_tab(tab)
+    if _nbytes(tab) < nb:
+        raise ValueError(f"tab holds fewer than neigh_tab_bytes({cap}) = {nb} bytes")
+    with _on_device(tab.device):
+        _check("wc_neigh_tab_init", _lib.active().wc_neigh_tab_init(
+            tab.data_ptr(), int(cap), _stream_ptr(stream, tab.device)))
+    return tab
+
+
+def neigh_apply(tab: torch.Tensor, updates: torch.Tensor, count: torch.Tensor,
+                m: Optional[int] = None, dropped: Optional[torch.Tensor] = None,
+                stream=None) -> torch.Tensor:
+    """neighbor_update for the records ``j < min(count, m)`` of ``updates`` (the
+    ``(m, 24)`` uint8 tensor rx_neigh_updates gives; ``m`` defaults to its
+    rows), applied to ``tab`` as if in order (wc_neigh_apply).  ``count`` is
+    read on the device.  Returns ``dropped``, a 1-element int64 device tensor
+    (accumulated into when given): the records with an af other than 0 / 4 / 6
+    or with a key a full table could not take.  Asynchronous; the scratch is
+    allocated here.  Calls on one table are ordered by the caller."""
+    _neigh_tab(tab)
+    d = tab.device
+    if not isinstance(updates, torch.Tensor) or updates.device != d or not updates.is_contiguous() \
+            or _nbytes(updates) % NEIGH_UPDATE.itemsize:
+        raise ValueError(f"updates must be the contiguous bytes of NEIGH_UPDATE records on {d}")
+    rows = _nbytes(updates) // NEIGH_UPDATE.itemsize
+    m = rows if m is None else int(m)
+    if not 0 <= m <= min(rows, _NEIGH_APPLY_MAX):
+        raise ValueError("m is at most the records in updates, and at most 2^31")
+    if not isinstance(count, torch.Tensor) or count.device != d or count.element_size() != 8 \
+            or count.numel() < 1:
+        raise ValueError(f"count must be an 8-byte count on {d}")
+    dropped = _bad_counter(dropped, d, "dropped")
+    scratch = _scratch(4 * m, d)
+    with _on_device(d):
+        _check("wc_neigh_apply", _lib.active().wc_neigh_apply(
+            tab.data_ptr(), updates.data_ptr() if m else None, count.data_ptr(), m,
+            dropped.data_ptr(), scratch.data_ptr(), _stream_ptr(stream, d)))
+    return dropped
+
+
+def _host_tab(tab: np.ndarray) -> np.ndarray:
+    t = np.ascontiguousarray(tab).reshape(-1).view(np.uint8)
+    if t.size < 64 + 32 * NEIGH_TAB_MIN_CAP or t.size % 4:
+        raise ValueError("tab must be a host copy of a neighbour table (tab.cpu().numpy())")
+    return np.ascontiguousarray(t.view(np.uint32))  # 4-byte aligned
+
+
+def neigh_tab_lookup(tab: np.ndarray, af: int, addr) -> Optional[bytes]:
+    """The MAC ``tab`` -- a host copy of a neighbour table -- holds for ``(af,
+    addr)``, or None (wc_neigh_tab_lookup: the device's own hash and probe, on
+    the host).  ``ValueError`` for an af other than 4 / 6 or bytes that are no
+    table."""
+    t = _host_tab(tab)
+    if af not in (4, 6):
+        raise ValueError("af is 4 or 6")
+    a = _addr_bytes(af, addr)
+    mac = (ctypes.c_uint8 * 6)()
+    rc = _lib.active().wc_neigh_tab_lookup(t.ctypes.data, int(af), a.ctypes.data, mac)
+    if rc == _WC_EINVAL:
+        raise ValueError("not a neighbour table: neigh_tab_init did not write these bytes")
+    _check("wc_neigh_tab_lookup", min(rc, 0))
+    return bytes(mac) if rc == 1 else None
+
+
+def neigh_tab_stats(tab: np.ndarray) -> Tuple[int, int]:
+    """``(cap, used)`` of a host copy of a neighbour table (wc_neigh_tab_stats)."""
+    t = _host_tab(tab)
+    cap, used = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = _lib.active().wc_neigh_tab_stats(t.ctypes.data, ctypes.byref(cap), ctypes.byref(used))
+    if rc == _WC_EINVAL:
+        raise ValueError("not a neighbour table: neigh_tab_init did not write these bytes")
+    _check("wc_neigh_tab_stats", rc)
+    return int(cap.value), int(used.value)
+
+
+def tx_resolve_scratch(ndst: int) -> int:
+    """Bytes of device scratch wc_tx_resolve needs for ndst destinations (no GPU)."""
+    return int(_lib.active().wc_tx_resolve_scratch(int(ndst)))
+
+
+def tx_resolve(tab: torch.Tensor, dsts: torch.Tensor, af: torch.Tensor, want_list: bool = True,
+               stream=None):
+    """The batched who_has (wc_tx_resolve): for every entry of ``dsts`` (the
+    bytes of a ``TX_DST`` array on the device, at most 65536) whose address, read
+    as family ``af[k]`` (uint8, 4 or 6), ``tab`` resolves to a MAC that is not
+    broadcast, that MAC is written into its ``dmac``; for the others ``dmac`` is
+    written ff x 6.  Returns ``(state uint8 NR_*, list, count)``: the ascending
+    indices with ``NR_MISS`` -- one per distinct unresolved address, the ones to
+    solicit -- as rx_select gives them (None, None with ``want_list=False``).
+    Asynchronous; the scratch is allocated here."""
+    _neigh_tab(tab)
+    d = tab.device
+    ndst = _table_tensor("dsts", dsts, TX_DST, _TX_BUILD_MAX_DSTS, d)
+    _byte_array("af", af, ndst, d)
+    state = torch.empty(ndst, dtype=torch.uint8, device=d)
+    lst = cnt = None
+    if want_list:
+        lst, _ = _index_list(None, ndst, d)
+        cnt = torch.zeros(1, dtype=torch.int64, device=d)
+    scratch = _scratch(tx_resolve_scratch(ndst), d)
+    with _on_device(d):
+        _check("wc_tx_resolve", _lib.active().wc_tx_resolve(
+            tab.data_ptr(), dsts.data_ptr() if ndst else None, af.data_ptr() if ndst else None,
+            ndst, state.data_ptr() if ndst else None, lst.data_ptr() if want_list else None,
+            cnt.data_ptr() if want_list else None, scratch.data_ptr(), _stream_ptr(stream, d)))
+    return state, (lst[:ndst] if want_list else None), cnt
+
+
+def tx_hold_plan(descs: torch.Tensor, socks: torch.Tensor, state: Optional[torch.Tensor],
+                 af: Optional[torch.Tensor], want_list: bool = True, stream=None,
+                 scratch: Optional[torch.Tensor] = None):
+    """Which frames of a TX batch wait for a neighbour (wc_tx_hold_plan):
+    ``descs`` / ``socks`` as tx_build_ragged takes them, ``state`` / ``af`` the
+    per-destination bytes of tx_resolve (None, None without destinations).
+    Returns ``(hold uint8 TH_*, list, count)``: the ``TH_HELD`` frames as
+    rx_select gives them (None, None with ``want_list=False``).  Asynchronous."""
+    if not isinstance(descs, torch.Tensor) or not descs.is_cuda:
+        raise ValueError("descs must be a device tensor")
+    d = descs.device
+    if not descs.is_contiguous() or _nbytes(descs) % TX_DESC.itemsize:
+        raise ValueError("descs must be the contiguous bytes of TX_DESC entries")
+    n = _nbytes(descs) // TX_DESC.itemsize
+    ns = _table_tensor("socks", socks, TX_SOCK, TX_BUILD_MAX_SOCKS, d)
+    if (state is None) != (af is None):
+        raise ValueError("state and af go together")
+    ndst = 0
+    if state is not None:
+        ndst = state.numel()
+        if ndst > _TX_BUILD_MAX_DSTS:
+            raise ValueError(f"at most {_TX_BUILD_MAX_DSTS} destinations")
+        _byte_array("state", state, ndst, d)
+        _byte_array("af", af, ndst, d)
+    hold = torch.empty(n, dtype=torch.uint8, device=d)
+    lst = cnt = None
+    if want_list:
+        lst, _ = _index_list(None, n, d)
+        cnt = torch.zeros(1, dtype=torch.int64, device=d)
+        scratch = _select_scratch(scratch, n, d)
+    with _on_device(d):
+        _check("wc_tx_hold_plan", _lib.active().wc_tx_hold_plan(
+            descs.data_ptr() if n else None, n, socks.data_ptr() if ns else None, ns,
+            state.data_ptr() if ndst else None, af.data_ptr() if ndst else None, ndst,
+            hold.data_ptr() if n else None, lst.data_ptr() if want_list else None,
+            cnt.data_ptr() if want_list else None, scratch.data_ptr() if want_list else None,
+            _stream_ptr(stream, d)))
+    return hold, (lst[:n] if want_list else None), cnt
+
+
+def tx_solicit_build(dsts: torch.Tensor, af: torch.Tensor, miss_list: torch.Tensor,
+                     count: torch.Tensor, engine: torch.Tensor, out: torch.Tensor,
+                     out_offsets: torch.Tensor, slot_bytes: int, stream=None, check: bool = True):
+    """Write the ARP who-has and neighbour solicitation frames for the
+    destinations tx_resolve listed (wc_tx_solicit_build), with rx_neigh_build's
+    contract: frame ``j < min(count, m)``, ``m = out_offsets.numel()``, solicits
+    ``dsts[miss_list[j]]`` at ``out[out_offsets[j]]``.  Returns ``(out_lens uint16
+    -- 0 where no frame was written --, built)``."""
+    d = out.device if isinstance(out, torch.Tensor) else None
+    ndst = _table_tensor("dsts", dsts, TX_DST, _TX_BUILD_MAX_DSTS, d)
+    _byte_array("af", af, ndst, d)
+    m, out_lens, built = _build_args("tx_resolve", dsts, ndst, "af", af, miss_list, count, engine,
+                                     out, out_offsets, slot_bytes, check)
+    with _on_device(d):
+        _check("wc_tx_solicit_build", _lib.active().wc_tx_solicit_build(
+            dsts.data_ptr() if ndst else None, af.data_ptr() if ndst else None, ndst,
+            miss_list.data_ptr(), count.data_ptr(), engine.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr() if m else None, m, int(slot_bytes),
+            out_lens.data_ptr() if m else None, built.data_ptr(), _stream_ptr(stream, d)))
+    return out_lens, built
+
+
 def tx_build_host(buf: np.ndarray, offsets: np.ndarray, descs: np.ndarray, socks: np.ndarray,
                   dsts: Optional[np.ndarray], slot_bytes: int,
                   zero_udp: bool = False) -> Tuple[np.ndarray, np.ndarray, int]:

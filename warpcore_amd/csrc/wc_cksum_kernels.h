@@ -285,6 +285,34 @@ hipError_t launch_tx_build(void *base, const uint64_t *offs, const void *desc, u
                            uint8_t *status, uint16_t *out_ip, uint16_t *out_udp, uint64_t *errors,
                            bool nt, hipStream_t st);
 
+// TX neighbours (wc_k_txneigh.hip; layout and steps in wc_tx_neigh.h).  Every
+// launch is at most as many workgroups as the device's `cus` compute units hold
+// at once (0: no cap), each striding.
+// Init: the table's tab_bytes(cap) bytes zeroed, magic and cap written.
+hipError_t launch_neigh_tab_init(void *tab, uint32_t cap, int cus, hipStream_t st);
+// Apply: records j < MIN(*count, m) of upd (struct wc_neigh_update, 4-byte
+// aligned) into the table, as if in order; scratch: m words; *dropped (optional)
+// accumulates, one atomic per workgroup.  Two launches; 1 <= m <= 2^31.
+hipError_t launch_neigh_apply(void *tab, const void *upd, const uint64_t *count, uint32_t m,
+                              uint64_t *dropped, void *scratch, int cus, hipStream_t st);
+// Resolve: state[k] and dsts[k].dmac for k < ndst (1 <= ndst <= 65536) from the
+// table and afs[k]; scratch: tx_resolve_set_bytes(ndst) bytes, 4-byte aligned,
+// zeroed here.  A memset and two launches.
+uint64_t tx_resolve_set_bytes(uint32_t ndst);
+hipError_t launch_tx_resolve(const void *tab, void *dsts, const uint8_t *afs, uint32_t ndst,
+                             uint8_t *state, void *scratch, int cus, hipStream_t st);
+// Hold plan: hold[i] = the enum wc_tx_hold code of frame i; one launch, n >= 1.
+hipError_t launch_tx_hold_plan(const void *desc, uint64_t n, const void *socks, uint32_t ns,
+                               const uint8_t *state, const uint8_t *afs, uint32_t ndst,
+                               uint8_t *hold, int cus, hipStream_t st);
+// Solicit build: as launch_rx_neigh_build, for the who-has and solicitation
+// frames of destinations list[j]; m >= 1, ndst >= 1.
+hipError_t launch_tx_solicit_build(const void *dsts, const uint8_t *afs, uint32_t ndst,
+                                   const uint32_t *list, const uint64_t *count, const void *eng,
+                                   void *out_base, const uint64_t *out_off, uint32_t m,
+                                   uint32_t slot_bytes, uint16_t *out_len, uint64_t *built, int cus,
+                                   hipStream_t st);
+
 // Resident small-batch server (wc_k_serve.hip).  Host-mapped pinned memory:
 // one record per packet, written by the host (seq last), polled / read by the
 // server's waves; one result slot per packet, written by the GPU in one
