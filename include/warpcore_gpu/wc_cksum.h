@@ -726,6 +726,60 @@ int wc_rx_neigh_build(const void *d_base, const uint64_t *d_off, const uint16_t 
                       void *d_out_base, const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
                       uint16_t *d_out_len, uint64_t *d_built, void *stream);
 
+/* --- RX drain: the whole per-ring RX plan in one call ---------------------- */
+
+/* What one poll of a netmap ring delivers is 256 to 4096 frames, and at that
+ * size the chain wc_rx_deliver_ragged -> wc_rx_demux -> wc_rx_reply_plan ->
+ * wc_rx_neigh_plan costs its seventeen launches and nothing else.  wc_rx_drain
+ * is that chain as one call: for n <= WC_RX_DRAIN_SMALL it is TWO launches
+ * (one wave per 64 frames for the six per-frame arrays, then one workgroup for
+ * the five lists and their counts); for a larger n it issues the four calls
+ * itself, so a caller has one entry point for any ring.  The build calls
+ * (wc_rx_reply_build, wc_rx_neigh_updates, wc_rx_neigh_build) and
+ * wc_neigh_apply follow it unchanged and consume its lists and counts.
+ *
+ * The contract: for every n, every output array holds exactly the bytes
+ *   wc_rx_deliver_ragged(d_base, d_off, d_frame_len, n, verdict, rec, NULL, NULL, drops, NULL, st);
+ *   wc_rx_demux(d_base, d_off, rec, n, d_tab, ns, sock, list, start, d_scratch, st);
+ *   wc_rx_reply_plan(d_base, d_off, d_frame_len, n, verdict, sock, d_eng, slot_bytes,
+ *                    action, reply_len, rlist, rcount, d_scratch, st);
+ *   wc_rx_neigh_plan(d_base, d_off, d_frame_len, n, action, d_eng,
+ *                    nact, nrlist, nrcount, ulist, ucount, d_scratch, st);
+ * leave there: list entries at and past a count keep what they held, all 256
+ * start entries are written, *drops is accumulated and the four counts (start
+ * [255], *rcount, *nrcount, *ucount) are written; no byte outside a frame is
+ * read, the RX buffer is not written, and the same input gives the same
+ * output.  Every member of *out is a device pointer with the alignment and
+ * size its call above asks for (rec: 16-byte aligned; the lists: n entries),
+ * and every member but drops is required.
+ *
+ * d_scratch: wc_rx_drain_scratch(n) bytes of device memory, 4-byte aligned,
+ * the caller's, one per call in flight -- enough for the calls above, which run
+ * one after another on the stream and share it.  The function is pure
+ * arithmetic, 0 for n = 0 and never decreasing in n.
+ *
+ * n = 0 is WC_OK: it writes the four zero counts and an all-zero start, and
+ * looks at no other pointer (d_base, d_tab, d_eng, d_scratch and the other
+ * members of *out may be NULL).  WC_EINVAL: a NULL out, n > 2^32, ns > 254, a
+ * NULL start / rcount / nrcount / ucount; and with n > 0: slot_bytes > 65535, a
+ * NULL d_base / d_off / d_frame_len / d_tab / d_eng or other required member,
+ * d_tab or d_eng not 4-byte aligned, rec not 16-byte aligned, a d_scratch that
+ * is NULL or not 4-byte aligned.  Asynchronous on `stream`, no library lock.
+ * The two launches: no workgroup waits for another, the only atomic is the drop
+ * count's (one per wave with a drop), all stores are plain vector stores. */
+#define WC_RX_DRAIN_SMALL 4096u
+
+struct wc_rx_drain_out {          /* device pointers; all required except drops */
+    uint8_t *verdict;  struct wc_rx_record *rec;  uint64_t *drops;  /* as wc_rx_deliver_ragged; drops accumulated, optional */
+    uint8_t *sock;     uint32_t *list;  uint64_t *start;            /* as wc_rx_demux: 256 start entries */
+    uint8_t *action;   uint16_t *reply_len;  uint32_t *rlist;  uint64_t *rcount;   /* as wc_rx_reply_plan, d_sock given */
+    uint8_t *nact;     uint32_t *nrlist; uint64_t *nrcount; uint32_t *ulist; uint64_t *ucount; /* as wc_rx_neigh_plan */
+};
+uint64_t wc_rx_drain_scratch(uint64_t n);
+int wc_rx_drain(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                const void *d_tab, uint32_t ns, const struct wc_rx_engine *d_eng, uint32_t slot_bytes,
+                const struct wc_rx_drain_out *out /* host struct */, void *d_scratch, void *stream);
+
 /* --- TX neighbours: device neighbour cache, batched who_has, solicitations - */
 
 /* What lies between "RX produces update records" and "TX consumes destination

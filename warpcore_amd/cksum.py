@@ -19,7 +19,7 @@ checksum on the CPU.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -920,6 +920,114 @@ def rx_neigh_build(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.
             out_offsets.data_ptr() if m else None, m, int(slot_bytes),
             out_lens.data_ptr() if m else None, built.data_ptr(), _stream_ptr(stream, d)))
     return out_lens, built
+
+
+# --------------------------------------------------------------------------
+# RX drain (rx_deliver_ragged -> rx_demux -> rx_reply_plan -> rx_neigh_plan as
+# one call: two launches for a ring of at most RX_DRAIN_SMALL frames).
+
+RX_DRAIN_SMALL = 4096  # WC_RX_DRAIN_SMALL
+
+
+class RxDrain(NamedTuple):
+    """The fifteen outputs of rx_drain, in struct wc_rx_drain_out's order."""
+    verdicts: torch.Tensor      # uint8 RX_*
+    records: torch.Tensor       # (n, 16) uint8: struct wc_rx_record
+    drops: torch.Tensor         # 1 int64, accumulated
+    sock: torch.Tensor          # uint8 socket ids
+    list: torch.Tensor          # uint32, grouped by socket
+    start: torch.Tensor         # 256 int64
+    actions: torch.Tensor       # uint8 RR_*
+    reply_lens: torch.Tensor    # uint16
+    reply_list: torch.Tensor    # uint32: RR_MASK_REPLY
+    reply_count: torch.Tensor   # 1 int64
+    nact: torch.Tensor          # uint8 RN_*
+    neigh_reply_list: torch.Tensor   # uint32: RN_MASK_REPLY
+    neigh_reply_count: torch.Tensor  # 1 int64
+    update_list: torch.Tensor   # uint32: RN_MASK_UPDATE
+    update_count: torch.Tensor  # 1 int64
+
+
+class _DrainOut(ctypes.Structure):  # struct wc_rx_drain_out
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "verdict", "rec", "drops", "sock", "list", "start", "action", "reply_len", "rlist",
+        "rcount", "nact", "nrlist", "nrcount", "ulist", "ucount")]
+
+
+def rx_drain_scratch(n: int) -> int:
+    """Bytes of device scratch wc_rx_drain needs for n frames (no GPU)."""
+    return int(_lib.active().wc_rx_drain_scratch(int(n)))
+
+
+def _drain_out(out: Optional[RxDrain], n: int, device) -> RxDrain:
+    """rx_drain's fifteen tensors: the caller's, checked, or allocated here."""
+    if out is None:
+        def lst():
+            return _index_list(None, n, device)[0]
+
+        def cnt():
+            return torch.zeros(1, dtype=torch.int64, device=device)
+        return RxDrain(torch.empty(n, dtype=torch.uint8, device=device),
+                       torch.empty((n, RX_RECORD.itemsize), dtype=torch.uint8, device=device),
+                       cnt(), torch.empty(n, dtype=torch.uint8, device=device), lst(),
+                       torch.zeros(_RX_STARTS, dtype=torch.int64, device=device),
+                       torch.empty(n, dtype=torch.uint8, device=device),
+                       torch.empty(n, dtype=torch.uint16, device=device), lst(), cnt(),
+                       torch.empty(n, dtype=torch.uint8, device=device), lst(), cnt(), lst(), cnt())
+    if not isinstance(out, RxDrain):
+        raise ValueError("out must be an RxDrain (an earlier call's result)")
+    for name in ("verdicts", "sock", "actions", "nact"):
+        _byte_array(name, getattr(out, name), n, device)
+    _byte_array("reply_lens", out.reply_lens, n, device, 2)
+    if not isinstance(out.records, torch.Tensor) or out.records.device != device \
+            or not out.records.is_contiguous() or _nbytes(out.records) < n * RX_RECORD.itemsize:
+        raise ValueError(f"records must be contiguous (n, 16) bytes on {device}")
+    for name in ("list", "reply_list", "neigh_reply_list", "update_list"):
+        _index_list(getattr(out, name), n, device)
+    for name, most in (("drops", 1), ("start", _RX_STARTS), ("reply_count", 1),
+                       ("neigh_reply_count", 1), ("update_count", 1)):
+        _byte_array(name, getattr(out, name), most, device, 8)
+    return out
+
+
+def rx_drain(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+             tab: torch.Tensor, ns: int, engine: torch.Tensor, slot_bytes: int = 2048,
+             out: Optional[RxDrain] = None, scratch: Optional[torch.Tensor] = None, stream=None,
+             check: bool = True) -> RxDrain:
+    """The whole per-ring RX plan in one call (wc_rx_drain): every output of
+    rx_deliver_ragged, rx_demux (``tab``: rx_socktab_build's bytes for ``ns``
+    sockets as a device tensor), rx_reply_plan (with the socket ids) and
+    rx_neigh_plan over the same frames, byte for byte -- two launches for at
+    most ``RX_DRAIN_SMALL`` frames, the four calls above that.  Returns an
+    ``RxDrain``; the lists hold ``max(n, 1)`` entries of which the first
+    ``count`` are written, ``drops`` is accumulated (zero in a tuple allocated
+    here).  ``out``: an earlier call's ``RxDrain`` to write into again;
+    ``scratch``: ``rx_drain_scratch(n)`` bytes, allocated here unless given --
+    give both per call in flight when ``stream`` is not the current stream.
+    The build calls (rx_reply_build, rx_neigh_updates, rx_neigh_build) take
+    its lists and counts unchanged.  Asynchronous."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
+    d = base.device
+    _same_device(base, tab=tab)
+    if not 0 <= int(ns) <= RX_DEMUX_MAX_SOCKS:
+        raise ValueError(f"ns must be 0..{RX_DEMUX_MAX_SOCKS}")
+    if not tab.is_contiguous() or _nbytes(tab) < rx_socktab_bytes(ns):
+        raise ValueError("tab must hold the rx_socktab_build bytes of ns sockets")
+    _engine_tensor(engine, d)
+    if not 0 <= int(slot_bytes) <= 0xFFFF:
+        raise ValueError("slot_bytes is at most 65535 (a frame length is a uint16)")
+    o = _drain_out(out, n, d)
+    if scratch is None:
+        scratch = _scratch(rx_drain_scratch(n), d)
+    elif _nbytes(scratch) < rx_drain_scratch(n) or scratch.device != d:
+        raise ValueError(f"scratch must hold rx_drain_scratch(n) bytes on {d}")
+    c_out = _DrainOut(*[t.data_ptr() or None for t in o])
+    with _on_device(d):
+        _check("wc_rx_drain", _lib.active().wc_rx_drain(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, _dev_ptr(tab), int(ns),
+            engine.data_ptr(), int(slot_bytes), ctypes.byref(c_out), scratch.data_ptr(),
+            _stream_ptr(stream, d)))
+    return o
 
 
 # --------------------------------------------------------------------------

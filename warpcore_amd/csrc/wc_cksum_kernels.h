@@ -260,6 +260,36 @@ hipError_t launch_rx_neigh_build(const void *base, const uint64_t *offs, const u
                                  const uint64_t *out_off, uint32_t m, uint32_t slot_bytes,
                                  uint16_t *out_len, uint64_t *built, int cus, hipStream_t st);
 
+// RX drain (wc_k_rxdrain.hip): for 0 <= n <= kRxDrainSmall frames, every output
+// array of launch_rx_verdict (with `rec`), launch_rx_demux, launch_rx_reply_plan
+// (sock given) and launch_rx_neigh_plan with their four lists (launch_rx_select
+// over the action and nact bytes), byte for byte, in two launches: one wave per
+// 64-frame tile for the six per-frame arrays, then one workgroup for the lists,
+// the 256 start entries and the three counts.  n = 0: the second launch alone,
+// which then reads no array.  Every pointer but drops is given; rec 16-byte,
+// table and eng 4-byte aligned; ns <= 254.
+constexpr uint32_t kRxDrainSmall = 4096; // WC_RX_DRAIN_SMALL
+struct RxDrainArrays {
+    uint8_t *verdict;
+    void *rec;
+    uint64_t *drops;
+    uint8_t *sock;
+    uint32_t *list;
+    uint64_t *start;
+    uint8_t *action;
+    uint16_t *reply_len;
+    uint32_t *rlist;
+    uint64_t *rcount;
+    uint8_t *nact;
+    uint32_t *nrlist;
+    uint64_t *nrcount;
+    uint32_t *ulist;
+    uint64_t *ucount;
+};
+hipError_t launch_rx_drain(const void *base, const uint64_t *offs, const uint16_t *flens,
+                           uint64_t n, const void *table, uint32_t ns, const void *eng,
+                           uint32_t slot_bytes, const RxDrainArrays &o, bool nt, hipStream_t st);
+
 // TX seal of Ethernet frames [base + offs[i], + flens[i]) (wc_k_tx.hip): both
 // checksums computed with their fields taken as 0 and stored raw into the
 // frame, status[i] its enum wc_tx_status code; out_ip / out_udp (optional)

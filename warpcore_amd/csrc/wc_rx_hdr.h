@@ -13,8 +13,11 @@
 //     RX reply and RX neighbour plans, wc_k_rxreply.hip / wc_k_rxneigh.hip);
 //   * the gathered stream of a tile's frames that need the UDP sum (FrameLds,
 //     frame_payload_cksum).
-// The two decision chains themselves (rx_decide, tx_decide) restate different
-// reference functions and stay with their kernels.
+//   * the RX decision chain and the delivery record (rx_decide, rx_record,
+//     rx_parse_rec, rx_parse_slow_rec), at the end of this file: the RX verdict
+//     kernels' and the RX drain kernel's (wc_k_rxdrain.hip).
+// The TX seal's chain (tx_decide) restates other reference functions and stays
+// with its kernel.
 #pragma once
 
 #include "wc_seg.h"
@@ -266,6 +269,133 @@ __device__ __forceinline__ uint32_t frame_payload_cksum(FrameLds &L, int lane, u
         wave_order(); // the tables are rewritten by the next tile
     }
     return r;
+}
+
+// --- the RX decision chain and the delivery record ---------------------------
+// What the RX verdict kernels (wc_k_rx.hip) and the RX drain kernel
+// (wc_k_rxdrain.hip) run on one parsed frame.
+
+// enum wc_rx_verdict (wc_cksum.h)
+constexpr uint32_t kRxOk = 0, kRxOkNoCksum = 1, kRxBadIpCksum = 2, kRxBadUdpCksum = 3,
+                   kRxShort = 4, kRxFragment = 5, kRxBadVersion = 6, kRxNotUdp = 7,
+                   kRxNotIp = 8, kRxTruncated = 9;
+
+__device__ __forceinline__ bool rx_is_drop(uint32_t v)
+{
+    return v != kRxOk && v != kRxOkNoCksum && v != kRxNotUdp && v != kRxNotIp;
+}
+
+struct RxParse {
+    uint64_t ip;      // the frame's IP header (frame + 14)
+    uint32_t plen;    // payload_cksum length udp_len + hl (need)
+    uint32_t verdict; // final unless need
+    bool need;        // the UDP checksum must be verified
+};
+
+// The reference's decision chain (eth_rx -> ip4_rx / ip6_rx -> udp_rx); bytes
+// past the frame only feed decisions that the length checks have made.
+__device__ __forceinline__ RxParse rx_decide(uint64_t fa, uint32_t flen, bool valid,
+                                             const RxHdr &x, uint32_t g0, uint16_t ipck)
+{
+    RxParse h{fa + 14u, 0u, kRxTruncated, false};
+    const bool v4 = x.v4, v6 = x.v6, frag = x.frag;
+    const uint32_t room = x.room, hl = x.hl, proto = x.proto, ip_plen = x.ip_plen;
+    const uint32_t ulen = ((g0 & 0xFFu) << 8) | ((g0 >> 8) & 0xFFu);
+    const bool ck_zero = (g0 >> 16) == 0u; // udp.c:132
+    const uint32_t udp_len = min(ulen, ip_plen); // udp.c:128
+    const uint32_t L = udp_len + hl;             // unwrapped; > 65535 is past any frame
+    const bool version_ok = x.version_ok, hdr_in = x.hdr_in, udp_in = x.udp_in;
+    uint32_t v;
+    if (flen < 14u)
+        v = kRxTruncated;
+    else if (!v4 && !v6)
+        v = kRxNotIp;
+    else if (room < 1u)
+        v = kRxTruncated;
+    else if (!version_ok)
+        v = kRxBadVersion;
+    else if (!hdr_in)
+        v = kRxTruncated;
+    else if (v4 && ipck != 0)
+        v = kRxBadIpCksum;
+    else if (frag)
+        v = kRxFragment;
+    else if (proto != 17u)
+        v = kRxNotUdp;
+    else if (ip_plen < 8u)
+        v = kRxShort;
+    else if (!udp_in)
+        v = kRxTruncated;
+    else if (ck_zero)
+        v = kRxOkNoCksum;
+    else if (room < max(L, 20u))
+        v = kRxTruncated;
+    else {
+        v = kRxOk;
+        h.need = valid;
+        h.plen = L;
+    }
+    h.verdict = v;
+    return h;
+}
+
+// struct wc_rx_record (wc_cksum.h) of a frame the parse accepts -- kRxOk here
+// is "OK unless the UDP sum then fails" --, 16 zero bytes for any other: what
+// udp_rx puts into the w_iov (udp.c:101-142, 163-165), as four little-endian
+// words.  Every field lies in bytes hdr_in and udp_in have placed inside the
+// frame.
+__device__ __forceinline__ u32x4 rx_record(const FrameHdr &f, uint32_t verdict)
+{
+    const uint32_t hl = f.x.hl;
+    const uint32_t g0 = f.g0;
+    const uint32_t ulen = ((g0 & 0xFFu) << 8) | ((g0 >> 8) & 0xFFu);
+    const uint32_t dlen = (min(ulen, f.x.ip_plen) - 8u) & 0xFFFFu; // udp.c:128-129, its wrap
+    const bool v4 = f.x.v4;
+    u32x4 r;
+    r.x = (14u + hl + 8u) | (dlen << 16);                    // data_off, data_len
+    r.y = f.pw;                                              // sport, dport as stored
+    r.z = (v4 ? 4u : 6u) | (f.tt << 8) | (hl << 24);         // af, tos, ttl, hl
+    r.w = v4 ? (26u | (30u << 16)) : (22u | (38u << 16));    // src_off, dst_off
+    // (masked, not selected against a zero vector: store data needs registers,
+    // and the compiler kept a hoisted {0, 0, 0, 0} live across the whole tile
+    // loop -- in scratch, at the 128-VGPR cap)
+    const uint32_t take = verdict == kRxOk || verdict == kRxOkNoCksum ? ~0u : 0u;
+    return u32x4{r.x & take, r.y & take, r.z & take, r.w & take};
+}
+
+// Sixteen zero bytes of store data made where they are stored (see rx_record).
+__device__ __forceinline__ u32x4 rx_zero_record()
+{
+    uint32_t z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    return u32x4{z, z, z, z};
+}
+
+// One record out, as a streaming (nontemporal) store.
+__device__ __forceinline__ void rx_rec_store(u32x4 *rec, uint64_t p, const u32x4 &r)
+{
+    __builtin_nontemporal_store(r, &rec[p]);
+}
+
+// rx_parse / rx_parse_slow for the DELIVER kernels: the same decision on a
+// parse that also returns the record's fields.
+__device__ __forceinline__ RxParse rx_parse_rec(const u32x4 (&c)[5], uint64_t fa, uint32_t flen,
+                                                bool valid, bool &slow, u32x4 &rec)
+{
+    const FrameHdr f = frame_hdr<true>(c, fa, flen);
+    slow = valid && f.x.hdr_in && f.x.v4 && (f.x.hl > 40u || f.x.hl < 20u);
+    const RxParse h = rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
+    rec = rx_record(f, slow ? kRxTruncated : h.verdict); // (a slow lane's comes from the slow parse)
+    return h;
+}
+
+__device__ __forceinline__ RxParse rx_parse_slow_rec(uint64_t fa, uint32_t flen, bool valid,
+                                                     uint64_t zero, u32x4 &rec)
+{
+    const FrameHdr f = frame_hdr_slow<true>(fa, flen, valid, zero);
+    const RxParse h = rx_decide(fa, flen, valid, f.x, f.g0, (uint16_t)f.ipck);
+    rec = rx_record(f, h.verdict);
+    return h;
 }
 
 } // namespace
