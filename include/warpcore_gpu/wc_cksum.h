@@ -931,6 +931,90 @@ int wc_tx_solicit_build(const struct wc_tx_dst *d_dsts, const uint8_t *d_af, uin
                         void *d_out_base, const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
                         uint16_t *d_out_len, uint64_t *d_built, void *stream);
 
+/* --- TX pump: the whole per-batch TX plan and build in one call ------------ */
+
+/* A TX burst is a ring's worth of frames to a few hundred destinations, and at
+ * that size wc_tx_resolve -> wc_tx_hold_plan -> wc_tx_solicit_build ->
+ * wc_tx_build_ragged costs a memset and eleven launches and nothing else -- and
+ * between the hold plan and the build the caller had to read d_hold back and
+ * compact the READY frames by hand, because the build takes no hold array.
+ * wc_tx_pump is that chain as one call with the build gated on the device: for
+ * n <= WC_TX_PUMP_SMALL frames and ndst <= WC_TX_PUMP_SMALL_DST destinations --
+ * with m <= WC_TX_PUMP_SMALL_DST solicitation slots: more than such a batch's
+ * destinations can fill take the other path, where a grid zeroes them -- it
+ * is TWO launches (one workgroup for the destinations, both lists and the
+ * solicitations; then one wave per 64 frames for the build); for a larger batch
+ * it issues the three calls itself and then the same gated build, so a caller
+ * has one entry point for any batch and no host round trip in either.
+ *
+ * The contract: for every n, ndst and m, every output -- the six dmac bytes of
+ * every d_dsts entry included -- holds exactly the bytes this sequence leaves:
+ *   wc_tx_resolve(d_tab, d_dsts, d_af, ndst, state, miss_list, miss_count, d_scratch, st);
+ *   wc_tx_hold_plan(d_desc, n, d_socks, ns, state, d_af, ndst, hold, held_list, held_count, d_scratch, st);
+ *   wc_tx_solicit_build(d_dsts, d_af, ndst, miss_list, miss_count, d_eng, d_sol_base, d_sol_off, m,
+ *                       sol_slot_bytes, sol_len, sol_built, st);
+ *   the gated build, per frame i:
+ *     hold[i] == WC_TH_READY      everything wc_tx_build_ragged does for that frame with the same
+ *                                 tables, slot_bytes and flags: the headers, frame_len, status, the
+ *                                 two optional values, its share of *errors.
+ *     hold[i] == WC_TH_MALFORMED  the frame is untouched, frame_len 0, status WC_TX_MALFORMED, and it
+ *                                 is counted in *errors.  Stricter than the build alone where
+ *                                 d_af[dst] is not the socket's family: the build would write that
+ *                                 frame, the pump refuses it.
+ *     hold[i] == WC_TH_HELD       the frame is untouched, frame_len 0, status WC_TX_PUMP_HELD, and it
+ *                                 is NOT counted in *errors.
+ *   Under both non-READY codes out_ip_hdr[i] and out_udp[i] are 0 where the arrays are given, and no
+ *   payload byte of the frame is read.
+ * WC_TX_PUMP_HELD is not an enum wc_tx_status code, and WC_TX_IS_ERROR is true
+ * for it: test hold[i] (or the held list) before applying the macro to a pump
+ * status.  List entries at and past a count keep what they held; the three
+ * counts are written, *errors is accumulated; nothing outside a frame or a
+ * solicitation slot is read or written; the same input gives the same output.
+ * The table is only read, and wc_tx_resolve's ordering rule against
+ * wc_neigh_apply carries over.  The frames and the solicitation slots must not
+ * overlap.  flags: WC_TX_ZERO_UDP_CKSUM or 0.
+ *
+ * Every member of *out is a device pointer with the size and alignment its call
+ * above asks for (state, miss_list: ndst entries; hold, held_list, frame_len,
+ * status, out_ip_hdr, out_udp: n; sol_len: m; the counts: 1).  out_ip_hdr,
+ * out_udp and errors are optional.  d_scratch: wc_tx_pump_scratch(n, ndst) bytes
+ * of device memory, 4-byte aligned, the caller's, one per call in flight --
+ * enough for the calls above, which share it.  The function is pure arithmetic:
+ * 0 for (0, 0) and for ndst > 65536, never decreasing in either argument.
+ *
+ * Empty sides are WC_OK.  n = 0: no frame-side pointer is looked at, *held_count
+ * is written 0.  ndst = 0: no destination-side pointer is looked at, *miss_count
+ * is written 0, *sol_built 0 and m zero lengths.  m = 0: no solicitation
+ * pointer is looked at but sol_built.
+ * WC_EINVAL, before a device is touched: a NULL out, a NULL miss_count /
+ * held_count / sol_built; n > 2^32, ns > 256, ndst > 65536; slot_bytes or
+ * sol_slot_bytes > 65535; a flag bit other than WC_TX_ZERO_UDP_CKSUM
+ * (WC_TX_NO_STORE included); and with the respective side non-empty every NULL
+ * or misaligned pointer its chain call refuses (a list is always asked for),
+ * which includes a NULL or not 4-byte-aligned d_scratch whenever n > 0 or ndst
+ * > 0, and a NULL sol_len with m > 0.  Asynchronous on `stream`, no library
+ * lock.  The two launches: no workgroup waits for another, nothing spins, every
+ * loop is bounded by n, ndst, m, the table's cap or the set's size; all global
+ * stores are plain vector stores, and the only global atomic is the error
+ * count's, one per wave with an error. */
+#define WC_TX_PUMP_SMALL     4096u   /* frames        */
+#define WC_TX_PUMP_SMALL_DST 4096u   /* destinations  */
+#define WC_TX_PUMP_HELD      0x80u   /* d_status of a HELD frame; not an enum wc_tx_status code */
+
+struct wc_tx_pump_out {              /* host struct of device pointers */
+    uint8_t *state;  uint32_t *miss_list;  uint64_t *miss_count;     /* as wc_tx_resolve   (ndst, ndst, 1) */
+    uint8_t *hold;   uint32_t *held_list;  uint64_t *held_count;     /* as wc_tx_hold_plan (n, n, 1)       */
+    uint16_t *sol_len;  uint64_t *sol_built;                         /* as wc_tx_solicit_build (m, 1)      */
+    uint16_t *frame_len;  uint8_t *status;                           /* as wc_tx_build_ragged (n, n)       */
+    uint16_t *out_ip_hdr;  uint16_t *out_udp;  uint64_t *errors;     /* optional; errors accumulated       */
+};
+uint64_t wc_tx_pump_scratch(uint64_t n, uint32_t ndst);
+int wc_tx_pump(const void *d_tab, struct wc_tx_dst *d_dsts, const uint8_t *d_af, uint32_t ndst,
+               const struct wc_tx_desc *d_desc, uint64_t n, const struct wc_tx_sock *d_socks, uint32_t ns,
+               void *d_base, const uint64_t *d_off, uint32_t slot_bytes, uint32_t flags,
+               const struct wc_rx_engine *d_eng, void *d_sol_base, const uint64_t *d_sol_off, uint32_t m,
+               uint32_t sol_slot_bytes, const struct wc_tx_pump_out *out, void *d_scratch, void *stream);
+
 /* --- host-memory batch (end-to-end: pinned H2D, kernel, D2H) ------------- */
 
 /* Same as wc_cksum_ragged, but every buffer is host memory: packet i is

@@ -68,6 +68,9 @@ SIGNATURES = {
     "wc_tx_hold_plan": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_solicit_build": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp,
                                    _vp]),
+    "wc_tx_pump_scratch": (_u64, [_u64, _u32]),
+    "wc_tx_pump": (_int, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp,
+                          _vp, _u32, _u32, _vp, _vp, _vp]),
     "wc_tx_seal_ragged": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "wc_tx_seal_host": (_int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp]),
     "wc_tx_socks_check": (_int, [_vp, _u32]),

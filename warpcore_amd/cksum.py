@@ -1385,6 +1385,147 @@ def tx_solicit_build(dsts: torch.Tensor, af: torch.Tensor, miss_list: torch.Tens
     return out_lens, built
 
 
+# --------------------------------------------------------------------------
+# TX pump (tx_resolve -> tx_hold_plan -> tx_solicit_build -> the build of the
+# READY frames as one call: two launches for a ring-sized batch).
+
+TX_PUMP_SMALL, TX_PUMP_SMALL_DST = 4096, 4096  # WC_TX_PUMP_SMALL, WC_TX_PUMP_SMALL_DST
+TX_PUMP_HELD = 0x80  # WC_TX_PUMP_HELD: the status of a TH_HELD frame, not a TX_* code
+
+
+class TxPump(NamedTuple):
+    """The thirteen outputs of tx_pump, in struct wc_tx_pump_out's order."""
+    state: torch.Tensor        # uint8 NR_*, per destination
+    miss_list: torch.Tensor    # uint32: NR_MASK_SOLICIT
+    miss_count: torch.Tensor   # 1 int64
+    hold: torch.Tensor         # uint8 TH_*, per frame
+    held_list: torch.Tensor    # uint32: TH_MASK_HELD
+    held_count: torch.Tensor   # 1 int64
+    sol_lens: torch.Tensor     # uint16, per solicitation slot
+    sol_built: torch.Tensor    # 1 int64
+    frame_lens: torch.Tensor   # uint16, 0 for a frame that was not built
+    status: torch.Tensor       # uint8 TX_*, or TX_PUMP_HELD
+    ip_hdr: torch.Tensor       # uint16
+    udp: torch.Tensor          # uint16
+    errors: torch.Tensor       # 1 int64, accumulated
+
+
+class _PumpOut(ctypes.Structure):  # struct wc_tx_pump_out
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "state", "miss_list", "miss_count", "hold", "held_list", "held_count", "sol_len",
+        "sol_built", "frame_len", "status", "out_ip_hdr", "out_udp", "errors")]
+
+
+def tx_pump_scratch(n: int, ndst: int) -> int:
+    """Bytes of device scratch wc_tx_pump needs for n frames to ndst
+    destinations (no GPU)."""
+    return int(_lib.active().wc_tx_pump_scratch(int(n), int(ndst)))
+
+
+def _pump_out(out: Optional[TxPump], n: int, ndst: int, m: int, device) -> TxPump:
+    """tx_pump's thirteen tensors: the caller's, checked, or allocated here."""
+    if out is None:
+        def arr(k, dtype):
+            return torch.empty(k, dtype=dtype, device=device)
+
+        def cnt():
+            return torch.zeros(1, dtype=torch.int64, device=device)
+        return TxPump(arr(ndst, torch.uint8), _index_list(None, ndst, device)[0], cnt(),
+                      arr(n, torch.uint8), _index_list(None, n, device)[0], cnt(),
+                      arr(m, torch.uint16), cnt(), arr(n, torch.uint16), arr(n, torch.uint8),
+                      arr(n, torch.uint16), arr(n, torch.uint16), cnt())
+    if not isinstance(out, TxPump):
+        raise ValueError("out must be a TxPump (an earlier call's result)")
+    _byte_array("state", out.state, ndst, device)
+    _byte_array("hold", out.hold, n, device)
+    _byte_array("status", out.status, n, device)
+    _byte_array("sol_lens", out.sol_lens, m, device, 2)
+    for name in ("frame_lens", "ip_hdr", "udp"):
+        _byte_array(name, getattr(out, name), n, device, 2)
+    _index_list(out.miss_list, ndst, device)
+    _index_list(out.held_list, n, device)
+    for name in ("miss_count", "held_count", "sol_built", "errors"):
+        _byte_array(name, getattr(out, name), 1, device, 8)
+    return out
+
+
+def tx_pump(tab: torch.Tensor, dsts: Optional[torch.Tensor], af: Optional[torch.Tensor],
+            descs: torch.Tensor, socks: torch.Tensor, base: torch.Tensor, offsets: torch.Tensor,
+            slot_bytes: int, engine: torch.Tensor, sol_out: torch.Tensor,
+            sol_offsets: torch.Tensor, sol_slot_bytes: int, zero_udp: bool = False,
+            out: Optional[TxPump] = None, scratch: Optional[torch.Tensor] = None, stream=None,
+            check: bool = True) -> TxPump:
+    """The whole per-batch TX plan and build in one call (wc_tx_pump): every
+    output of tx_resolve (``dsts`` / ``af``: the destination table and its
+    family bytes, None, None without destinations), tx_hold_plan (``descs`` /
+    ``socks``) and tx_solicit_build (``engine``, one solicitation per slot of
+    ``sol_offsets`` in ``sol_out``) with their lists, byte for byte, and then the
+    build of tx_build_ragged for the ``TH_READY`` frames alone: a ``TH_HELD``
+    frame is untouched, has length 0 and status ``TX_PUMP_HELD`` and is not
+    counted in ``errors``; a ``TH_MALFORMED`` one is untouched, ``TX_MALFORMED``
+    and counted.  Two launches for at most ``TX_PUMP_SMALL`` frames to at most
+    ``TX_PUMP_SMALL_DST`` destinations, the chain's calls and the same gated
+    build above that; no host round trip in either.  Returns a ``TxPump``; the
+    lists hold ``max(n, 1)`` / ``max(ndst, 1)`` entries of which the first
+    ``count`` are written.  ``out``: an earlier call's ``TxPump`` to write into
+    again (``errors`` is accumulated); ``scratch``: ``tx_pump_scratch(n, ndst)``
+    bytes, allocated here unless given -- give both per call in flight when
+    ``stream`` is not the current stream.  The caller keeps every frame's slot
+    inside ``base``; under ``check`` every solicitation slot is kept inside
+    ``sol_out`` and ``sol_out`` off ``base``.  Asynchronous."""
+    _same_device(base, offsets=offsets, descs=descs, socks=socks, dsts=dsts, sol_out=sol_out,
+                 sol_offsets=sol_offsets)
+    d = base.device
+    _neigh_tab(tab)
+    if tab.device != d:
+        raise ValueError(f"tab must be on {d}")
+    if not base.is_contiguous() or base.element_size() != 1:
+        raise ValueError("base must be a contiguous 1-byte tensor (the frames are written in place)")
+    n = offsets.numel()
+    if offsets.element_size() != 8 or offsets.is_floating_point() or not offsets.is_contiguous():
+        raise ValueError("offsets must be contiguous 8-byte integers")
+    if not descs.is_contiguous() or _nbytes(descs) != n * TX_DESC.itemsize:
+        raise ValueError("descs must be the contiguous bytes of one TX_DESC per frame")
+    ns = _table_tensor("socks", socks, TX_SOCK, TX_BUILD_MAX_SOCKS, d)
+    if (dsts is None) != (af is None):
+        raise ValueError("dsts and af go together")
+    ndst = 0 if dsts is None else _table_tensor("dsts", dsts, TX_DST, _TX_BUILD_MAX_DSTS, d)
+    if ndst:
+        _byte_array("af", af, ndst, d)
+    _engine_tensor(engine, d)
+    if not sol_out.is_contiguous() or sol_out.element_size() != 1:
+        raise ValueError("sol_out must be a contiguous 1-byte tensor")
+    m = sol_offsets.numel()
+    if sol_offsets.element_size() != 8 or sol_offsets.is_floating_point() \
+            or not sol_offsets.is_contiguous() or m > 0xFFFFFFFF:
+        raise ValueError("sol_offsets must be contiguous 8-byte integers, at most 2^32 - 1")
+    if not 0 <= int(slot_bytes) <= 0xFFFF or not 0 <= int(sol_slot_bytes) <= 0xFFFF:
+        raise ValueError("slot_bytes and sol_slot_bytes are at most 65535")
+    if check and m:
+        so = sol_offsets.view(torch.int64)
+        if bool((so < 0).any()) or int(so.max()) + int(sol_slot_bytes) > _nbytes(sol_out):
+            raise ValueError("a solicitation slot [off, off + sol_slot_bytes) runs past sol_out")
+        ob, oe = sol_out.data_ptr(), sol_out.data_ptr() + _nbytes(sol_out)
+        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
+            raise ValueError("sol_out overlaps base: frames and solicitation slots must not overlap")
+    o = _pump_out(out, n, ndst, m, d)
+    need = tx_pump_scratch(n, ndst)
+    if scratch is None:
+        scratch = _scratch(need, d)
+    elif _nbytes(scratch) < need or scratch.device != d:
+        raise ValueError(f"scratch must hold tx_pump_scratch(n, ndst) bytes on {d}")
+    c_out = _PumpOut(*[t.data_ptr() or None for t in o])
+    with _on_device(d):
+        _check("wc_tx_pump", _lib.active().wc_tx_pump(
+            tab.data_ptr(), dsts.data_ptr() if ndst else None, af.data_ptr() if ndst else None,
+            ndst, descs.data_ptr() if n else None, n, socks.data_ptr() if ns else None, ns,
+            base.data_ptr() if n else None, offsets.data_ptr() if n else None, int(slot_bytes),
+            _TX_ZERO_UDP_CKSUM if zero_udp else 0, engine.data_ptr(),
+            sol_out.data_ptr() if m else None, sol_offsets.data_ptr() if m else None, m,
+            int(sol_slot_bytes), ctypes.byref(c_out), scratch.data_ptr(), _stream_ptr(stream, d)))
+    return o
+
+
 def tx_build_host(buf: np.ndarray, offsets: np.ndarray, descs: np.ndarray, socks: np.ndarray,
                   dsts: Optional[np.ndarray], slot_bytes: int,
                   zero_udp: bool = False) -> Tuple[np.ndarray, np.ndarray, int]:

@@ -343,6 +343,37 @@ hipError_t launch_tx_solicit_build(const void *dsts, const uint8_t *afs, uint32_
                                    uint32_t slot_bytes, uint16_t *out_len, uint64_t *built, int cus,
                                    hipStream_t st);
 
+// TX pump (wc_k_txpump.hip, wc_k_txbuild.hip; the gate and the destination
+// steps in wc_tx_pump.h).  Plan: for 0 <= n <= tp::kSmall frames, 0 <= ndst <=
+// tp::kSmallDst destinations and 0 <= m <= tp::kSmallDst solicitation slots,
+// every output of launch_tx_resolve,
+// launch_tx_hold_plan (both with their launch_rx_select lists) and
+// launch_tx_solicit_build, byte for byte, from one workgroup; the three counts
+// are always written.  An empty side's pointers are not looked at (m = 0: none
+// of the solicitation side but sol_built).
+struct TxPumpArrays {
+    uint8_t *state;
+    uint32_t *miss_list;
+    uint64_t *miss_count;
+    uint8_t *hold;
+    uint32_t *held_list;
+    uint64_t *held_count;
+    uint16_t *sol_len;
+    uint64_t *sol_built;
+};
+hipError_t launch_tx_pump_plan(const void *tab, void *dsts, const uint8_t *afs, uint32_t ndst,
+                               const void *desc, uint32_t n, const void *socks, uint32_t ns,
+                               const void *eng, void *sol_base, const uint64_t *sol_off, uint32_t m,
+                               uint32_t sol_slot_bytes, const TxPumpArrays &o, hipStream_t st);
+// Gated build: launch_tx_build's frame for any n >= 1, with hold[i] (enum
+// wc_tx_hold) deciding per frame by tp::gate: only a READY frame is built.
+// flags: kTxZeroUdp or 0.
+hipError_t launch_tx_build_gated(void *base, const uint64_t *offs, const void *desc, uint64_t n,
+                                 const void *socks, uint32_t ns, const void *dsts, uint32_t ndst,
+                                 uint32_t slot_bytes, uint32_t flags, const uint8_t *hold,
+                                 uint16_t *frame_len, uint8_t *status, uint16_t *out_ip,
+                                 uint16_t *out_udp, uint64_t *errors, bool nt, hipStream_t st);
+
 // Resident small-batch server (wc_k_serve.hip).  Host-mapped pinned memory:
 // one record per packet, written by the host (seq last), polled / read by the
 // server's waves; one result slot per packet, written by the GPU in one

@@ -47,6 +47,7 @@
 // Roofline: HBM, the payload bytes once.
 #include "wc_rx_hdr.h"
 #include "wc_tx_build.h"
+#include "wc_tx_pump.h"
 
 namespace wc {
 namespace {
@@ -64,18 +65,21 @@ __device__ __forceinline__ void txb_meta_load(const uint64_t *__restrict__ offs,
 
 constexpr int kTxbSpan = 15; // XCD super-blocks of 2^15 tiles, as the seal's
 
-// One-wave workgroups and 4 waves per SIMD, as k_tx_seal.  STORE = false
-// (WC_TX_NO_STORE): the frames are only read.
-template <bool NT, bool STORE>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
-k_tx_build(uint8_t *base, const uint64_t *__restrict__ offs, const uint2 *__restrict__ desc,
-           uint64_t n, const uint32_t *__restrict__ socks, uint32_t ns,
-           const uint32_t *__restrict__ dsts, uint32_t ndst, uint32_t slot_bytes,
-           uint32_t zero_udp_flag, uint16_t *__restrict__ frame_len, uint8_t *__restrict__ status,
-           uint16_t *__restrict__ out_ip, uint16_t *__restrict__ out_udp,
-           unsigned long long *__restrict__ errors)
+// The body of both build kernels.  STORE = false (WC_TX_NO_STORE): the frames
+// are only read.  GATED (the TX pump's build): one more
+// per-frame byte, hold[p], and tp::gate in the place of the ungated kernel's
+// three lines -- `built` additionally requires WC_TH_READY, so no payload byte
+// of another frame is streamed and no header byte of it stored.
+template <bool NT, bool STORE, bool GATED>
+__device__ __forceinline__ void
+tx_build_body(FrameLds &L, uint8_t *base, const uint64_t *__restrict__ offs,
+              const uint2 *__restrict__ desc, uint64_t n, const uint32_t *__restrict__ socks,
+              uint32_t ns, const uint32_t *__restrict__ dsts, uint32_t ndst, uint32_t slot_bytes,
+              uint32_t zero_udp_flag, const uint8_t *__restrict__ hold,
+              uint16_t *__restrict__ frame_len, uint8_t *__restrict__ status,
+              uint16_t *__restrict__ out_ip, uint16_t *__restrict__ out_udp,
+              unsigned long long *__restrict__ errors)
 {
-    __shared__ FrameLds L;
     using Src = GathSrc<kFrameUns, NT, false>;
 
     const int lane = threadIdx.x & 63;
@@ -97,6 +101,9 @@ k_tx_build(uint8_t *base, const uint64_t *__restrict__ offs, const uint2 *__rest
         const uint64_t fa = (uint64_t)(uintptr_t)base + off_n;
         const txb::Desc d = txb::desc_of(desc_n.x, desc_n.y);
         txb_meta_load(offs, desc, (tile + nwaves) * 64 + lane, n, off_n, desc_n);
+        uint32_t hold_p = 0u;
+        if constexpr (GATED)
+            hold_p = hold[valid ? p : 0];
 
         // The table entries, only where the index lies inside the table.
         const bool sock_in = valid && d.sock < ns, dst_in = valid && d.dst < ndst;
@@ -114,7 +121,10 @@ k_tx_build(uint8_t *base, const uint64_t *__restrict__ offs, const uint2 *__rest
                 t[k] = e[k];
         }
         const txb::Decide x = txb::decide(sock_in, w[0], dst_in, d.data_len, slot_bytes, zero_udp);
-        const bool built = valid && x.status <= txb::kSealedZeroUdp;
+        tp::Gate g{x.status, x.flen, x.status <= txb::kSealedZeroUdp, false};
+        if constexpr (GATED)
+            g = tp::gate(hold_p, x);
+        const bool built = valid && g.built;
         const bool need = built && !zero_udp && d.data_len != 0u;
 
         // ~ip_cksum(payload, data_len) of the lanes with `need`
@@ -140,20 +150,54 @@ k_tx_build(uint8_t *base, const uint64_t *__restrict__ offs, const uint2 *__rest
                 txb::store_headers(GlobalMem{}, fa, x.v4, h.h);
         }
         if (valid) {
-            status[p] = (uint8_t)x.status;
+            status[p] = (uint8_t)g.status;
             frame_len[p] = (uint16_t)(built ? x.flen : 0u);
             if (out_ip)
                 out_ip[p] = (uint16_t)(built ? h.ip_hdr : 0u);
             if (out_udp)
                 out_udp[p] = (uint16_t)(built ? h.udp : 0u);
         }
-        nerr += valid && !built;
+        if constexpr (GATED)
+            nerr += valid && g.error;
+        else
+            nerr += valid && !built;
     }
     if (errors) {
         nerr = group_sum<64>(nerr);
         if (lane == 0 && nerr)
             atomicAdd(errors, (unsigned long long)nerr);
     }
+}
+
+// One-wave workgroups and 4 waves per SIMD, as k_tx_seal.
+template <bool NT, bool STORE>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
+k_tx_build(uint8_t *base, const uint64_t *__restrict__ offs, const uint2 *__restrict__ desc,
+           uint64_t n, const uint32_t *__restrict__ socks, uint32_t ns,
+           const uint32_t *__restrict__ dsts, uint32_t ndst, uint32_t slot_bytes,
+           uint32_t zero_udp_flag, uint16_t *__restrict__ frame_len, uint8_t *__restrict__ status,
+           uint16_t *__restrict__ out_ip, uint16_t *__restrict__ out_udp,
+           unsigned long long *__restrict__ errors)
+{
+    __shared__ FrameLds L;
+    tx_build_body<NT, STORE, false>(L, base, offs, desc, n, socks, ns, dsts, ndst, slot_bytes,
+                                    zero_udp_flag, nullptr, frame_len, status, out_ip, out_udp,
+                                    errors);
+}
+
+template <bool NT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
+k_tx_build_gated(uint8_t *base, const uint64_t *__restrict__ offs, const uint2 *__restrict__ desc,
+                 uint64_t n, const uint32_t *__restrict__ socks, uint32_t ns,
+                 const uint32_t *__restrict__ dsts, uint32_t ndst, uint32_t slot_bytes,
+                 uint32_t zero_udp_flag, const uint8_t *__restrict__ hold,
+                 uint16_t *__restrict__ frame_len, uint8_t *__restrict__ status,
+                 uint16_t *__restrict__ out_ip, uint16_t *__restrict__ out_udp,
+                 unsigned long long *__restrict__ errors)
+{
+    __shared__ FrameLds L;
+    tx_build_body<NT, true, true>(L, base, offs, desc, n, socks, ns, dsts, ndst, slot_bytes,
+                                  zero_udp_flag, hold, frame_len, status, out_ip, out_udp, errors);
 }
 
 } // namespace
@@ -188,6 +232,27 @@ hipError_t launch_tx_build(void *base, const uint64_t *offs, const void *desc, u
     WC_TXB(true, true) WC_TXB(true, false) WC_TXB(false, true) WC_TXB(false, false)
 #undef WC_TXB
     return hipErrorInvalidValue; // (every combination is listed above)
+}
+
+hipError_t launch_tx_build_gated(void *base, const uint64_t *offs, const void *desc, uint64_t n,
+                                 const void *socks, uint32_t ns, const void *dsts, uint32_t ndst,
+                                 uint32_t slot_bytes, uint32_t flags, const uint8_t *hold,
+                                 uint16_t *frame_len, uint8_t *status, uint16_t *out_ip,
+                                 uint16_t *out_udp, uint64_t *errors, bool nt, hipStream_t st)
+{
+    const int grid = tile_grid(n);
+    const uint32_t zu = (flags & kTxZeroUdp) ? 1u : 0u;
+#define WC_TXG(N)                                                              \
+    hipLaunchKernelGGL((k_tx_build_gated<N>), dim3(grid), dim3(64), 0, st, (uint8_t *)base, offs, \
+                       (const uint2 *)desc, n, (const uint32_t *)socks, ns, (const uint32_t *)dsts, \
+                       ndst, slot_bytes, zu, hold, frame_len, status, out_ip, out_udp,            \
+                       (unsigned long long *)errors)
+    if (nt)
+        WC_TXG(true);
+    else
+        WC_TXG(false);
+#undef WC_TXG
+    return hipGetLastError();
 }
 
 } // namespace wc

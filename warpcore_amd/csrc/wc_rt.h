@@ -463,6 +463,46 @@ int rx_list_build(uint64_t n, uint32_t m, uint32_t slot_bytes, bool ptrs, uint16
     return hip_err(e);
 }
 
+// --- wc_rt_tx.cpp, wc_rt_txneigh.cpp, wc_rt_txpump.cpp ------------------------
+// The pointer rules of the TX build and TX neighbour calls on a non-empty
+// side, each stated once: the call itself and wc_tx_pump refuse the same.
+// The argument rules both build calls share (n > 0; wc_rt_tx.cpp).
+int tx_build_args(const void *base, const void *off, const void *desc, const void *socks,
+                  uint32_t ns, const void *dsts, uint32_t ndst, const void *frame_len,
+                  const void *status);
+
+// wc_tx_resolve, ndst > 0.
+inline bool tx_resolve_ptrs_ok(const void *d_tab, const void *d_dsts, const void *d_af,
+                               const void *d_state, const void *d_scratch)
+{
+    if (!d_tab || !d_dsts || !d_af || !d_state || !d_scratch)
+        return false;
+    return !(((uintptr_t)d_tab & 15u) || ((uintptr_t)d_dsts & 3u) || ((uintptr_t)d_scratch & 3u));
+}
+
+// wc_tx_hold_plan, n > 0.
+inline bool tx_hold_ptrs_ok(const void *d_desc, const void *d_hold, const void *d_socks, uint32_t ns,
+                            const void *d_state, const void *d_af, uint32_t ndst, bool list,
+                            const void *d_scratch)
+{
+    if (!d_desc || ((uintptr_t)d_desc & 7u) || !d_hold)
+        return false;
+    if (ns != 0 && (!d_socks || ((uintptr_t)d_socks & 3u)))
+        return false;
+    if (ndst != 0 && (!d_state || !d_af))
+        return false;
+    return rx_scratch_ok(list, d_scratch);
+}
+
+// wc_tx_solicit_build, m > 0 and ndst > 0 (rx_list_build's `ptrs`).
+inline bool tx_solicit_ptrs_ok(const void *d_dsts, const void *d_af, const void *d_list,
+                               const void *d_count, const void *d_eng, const void *d_out_base,
+                               const void *d_out_off)
+{
+    return d_dsts && !((uintptr_t)d_dsts & 3u) && d_af && d_list && d_count && d_eng &&
+           !((uintptr_t)d_eng & 3u) && d_out_base && d_out_off;
+}
+
 // --- wc_rt_server.cpp ---------------------------------------------------------
 constexpr int kSrvFallback = 1; // serve_batch: not served, take the launch path
 // One small registered batch through the server (caller holds g_mu, the

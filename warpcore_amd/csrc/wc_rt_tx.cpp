@@ -114,10 +114,13 @@ int wc_tx_socks_check(const struct wc_tx_sock *socks, uint32_t ns)
     return WC_OK;
 }
 
-// The argument rules both build calls share (n > 0), before a device is touched.
-static int tx_build_args(const void *base, const void *off, const void *desc, const void *socks,
-                         uint32_t ns, const void *dsts, uint32_t ndst, const void *frame_len,
-                         const void *status)
+} // extern "C"
+
+// The argument rules both build calls (and wc_tx_pump) share (n > 0), before a
+// device is touched.
+int wc::rt::tx_build_args(const void *base, const void *off, const void *desc, const void *socks,
+                          uint32_t ns, const void *dsts, uint32_t ndst, const void *frame_len,
+                          const void *status)
 {
     if (!base || !off || !desc || !frame_len || !status)
         return WC_EINVAL;
@@ -127,6 +130,8 @@ static int tx_build_args(const void *base, const void *off, const void *desc, co
         return WC_EINVAL;
     return WC_OK;
 }
+
+extern "C" {
 
 int wc_tx_build_ragged(void *d_base, const uint64_t *d_off, const struct wc_tx_desc *d_desc,
                        uint64_t n, const struct wc_tx_sock *d_socks, uint32_t ns,

@@ -128,9 +128,7 @@ int wc_tx_resolve(const void *d_tab, struct wc_tx_dst *d_dsts, const uint8_t *d_
     hipStream_t st = (hipStream_t)stream;
     if (ndst == 0)
         return rx_zero_counts(d_count, nullptr, st);
-    if (!d_tab || !d_dsts || !d_af || !d_state || !d_scratch)
-        return WC_EINVAL;
-    if (((uintptr_t)d_tab & 15u) || ((uintptr_t)d_dsts & 3u) || ((uintptr_t)d_scratch & 3u))
+    if (!tx_resolve_ptrs_ok(d_tab, d_dsts, d_af, d_state, d_scratch))
         return WC_EINVAL;
     Ready R;
     if (R.rc)
@@ -153,13 +151,8 @@ int wc_tx_hold_plan(const struct wc_tx_desc *d_desc, uint64_t n, const struct wc
     hipStream_t st = (hipStream_t)stream;
     if (n == 0)
         return rx_zero_counts(d_count, nullptr, st);
-    if (!d_desc || ((uintptr_t)d_desc & 7u) || !d_hold)
-        return WC_EINVAL;
-    if (ns != 0 && (!d_socks || ((uintptr_t)d_socks & 3u)))
-        return WC_EINVAL;
-    if (ndst != 0 && (!d_state || !d_af))
-        return WC_EINVAL;
-    if (!rx_scratch_ok(d_list != nullptr, d_scratch))
+    if (!tx_hold_ptrs_ok(d_desc, d_hold, d_socks, ns, d_state, d_af, ndst, d_list != nullptr,
+                         d_scratch))
         return WC_EINVAL;
     Ready R;
     if (R.rc)
@@ -179,8 +172,8 @@ int wc_tx_solicit_build(const struct wc_tx_dst *d_dsts, const uint8_t *d_af, uin
 {
     if (ndst > tn::kResolveMax)
         return WC_EINVAL;
-    const bool ptrs = d_dsts && !((uintptr_t)d_dsts & 3u) && d_af && d_list && d_count && d_eng &&
-                      !((uintptr_t)d_eng & 3u) && d_out_base && d_out_off;
+    const bool ptrs =
+        tx_solicit_ptrs_ok(d_dsts, d_af, d_list, d_count, d_eng, d_out_base, d_out_off);
     return rx_list_build(ndst, m, slot_bytes, ptrs, d_out_len, d_built, (hipStream_t)stream,
                          [&](int cus) {
                              return wc::launch_tx_solicit_build(d_dsts, d_af, ndst, d_list, d_count,
