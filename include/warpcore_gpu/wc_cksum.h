@@ -780,6 +780,78 @@ int wc_rx_drain(const void *d_base, const uint64_t *d_off, const uint16_t *d_fra
                 const void *d_tab, uint32_t ns, const struct wc_rx_engine *d_eng, uint32_t slot_bytes,
                 const struct wc_rx_drain_out *out /* host struct */, void *d_scratch, void *stream);
 
+/* --- RX answer: the builds behind the drain and the apply in one call ------ */
+
+/* Behind every drain the caller ran wc_rx_reply_build, wc_rx_neigh_updates,
+ * wc_rx_neigh_build and wc_neigh_apply ("TX neighbours" below): five launches
+ * and two memsets for the handful of frames of a ring that want an answer or
+ * carry a neighbour update.  wc_rx_answer is that chain as one call: with r_m,
+ * n_m and u_m all <= WC_RX_ANSWER_SMALL (and, where tab is given, u_m <=
+ * WC_RX_ANSWER_SMALL_APPLY) it is TWO launches and no memset (one
+ * grid whose workgroups are split between the three builds, then one workgroup
+ * for the two built counts and the apply); above any of them it issues the
+ * four calls itself, so a caller has one entry point for any size.  A ring turn
+ * on the device is wc_rx_drain -> wc_rx_answer -> wc_tx_pump, two launches each,
+ * with no host read in between.
+ *
+ * The contract: for every n and every r_m / n_m / u_m, every output holds
+ * exactly what this chain leaves there, run on the same stream:
+ *   wc_rx_reply_build  (d_base, d_off, d_frame_len, n, action, rlist,  rcount,  d_eng, r_out_base, r_out_off, r_m, slot_bytes, ip_id, r_out_len, r_built, st);
+ *   wc_rx_neigh_updates(d_base, d_off, d_frame_len, n, nact,   ulist,  ucount,  u_m, upd, st);
+ *   wc_rx_neigh_build  (d_base, d_off, d_frame_len, n, nact,   nrlist, nrcount, d_eng, n_out_base, n_out_off, n_m, slot_bytes, n_out_len, n_built, st);
+ *   if (tab) wc_neigh_apply(tab, upd, ucount, u_m, dropped, d_scratch, st);
+ * byte for byte: the slots, with nothing outside [slot, slot + length) written;
+ * both length arrays over all m entries; both built counts, written and not
+ * accumulated; all u_m records, the zero ones included.  For the table the
+ * contract is wc_neigh_apply's own, not byte for byte: read through lookups it
+ * is the chain's; which new keys a full table keeps stays unspecified; which
+ * entry a key lands in may differ; *dropped is accumulated by the same number.
+ * The RX buffer is not written, no byte outside a frame is read, and the same
+ * input gives the same output.  Every rule of the four calls holds for its
+ * part: m = 0 looks at no pointer of that part, except that both built counts
+ * are always written; n = 0 gives zero lengths and zero records; a stale action
+ * byte or a list index >= n gives length 0 and an untouched slot.
+ * One precondition the chain does not have: the reply slots and the neighbour
+ * slots must not overlap each other -- they now belong to one launch, where the
+ * chain would simply have overwritten.
+ *
+ * d_scratch: wc_rx_answer_scratch(u_m) = wc_neigh_apply_scratch(u_m) bytes of
+ * device memory, 4-byte aligned, the caller's, one per call in flight; required
+ * only when tab != NULL and u_m > 0.  Pure arithmetic, 0 at 0 and never
+ * decreasing (the two launches use none, but ask for the same).
+ *
+ * WC_EINVAL, before a device is touched: a NULL io, r_built or n_built; n >
+ * 2^32; slot_bytes > 65535; for each part with m > 0 (and n > 0 where its call
+ * says so) the NULL and alignment rules of its call; with tab and u_m > 0,
+ * wc_neigh_apply's rules for tab, upd, ucount and d_scratch.  Asynchronous on
+ * `stream`, no library lock.  The two launches: no workgroup waits for another,
+ * nothing spins, all stores are plain vector stores or the table's own atomics
+ * (and one atomic add on *dropped). */
+#define WC_RX_ANSWER_SMALL 4096u        /* entries per list: r_m, n_m and u_m */
+#define WC_RX_ANSWER_SMALL_APPLY 1024u  /* u_m where tab is given: one workgroup's claim and
+                                         * commit of more records measured slower than the chain */
+
+struct wc_rx_answer_io {                /* host struct; device pointers */
+    /* in: what wc_rx_drain (or the two plans) left */
+    const uint8_t *action;  const uint32_t *rlist;  const uint64_t *rcount;
+    const uint8_t *nact;    const uint32_t *nrlist; const uint64_t *nrcount;
+    const uint32_t *ulist;  const uint64_t *ucount;
+    /* replies, as wc_rx_reply_build */
+    void *r_out_base; const uint64_t *r_out_off; uint32_t r_m;
+    const uint16_t *ip_id /* optional */; uint16_t *r_out_len; uint64_t *r_built;
+    /* ARP is-at / neighbour advertisements, as wc_rx_neigh_build */
+    void *n_out_base; const uint64_t *n_out_off; uint32_t n_m;
+    uint16_t *n_out_len; uint64_t *n_built;
+    /* update records, as wc_rx_neigh_updates */
+    uint32_t u_m; struct wc_neigh_update *upd;
+    /* the device neighbour cache, as wc_neigh_apply; tab NULL: no apply */
+    void *tab; uint64_t *dropped /* optional, accumulated */;
+};
+uint64_t wc_rx_answer_scratch(uint32_t u_m);
+int wc_rx_answer(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+                 const struct wc_rx_engine *d_eng, uint32_t slot_bytes,
+                 const struct wc_rx_answer_io *io /* host struct */, void *d_scratch, void *stream);
+
 /* --- TX neighbours: device neighbour cache, batched who_has, solicitations - */
 
 /* What lies between "RX produces update records" and "TX consumes destination

@@ -1031,6 +1031,130 @@ def rx_drain(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor
 
 
 # --------------------------------------------------------------------------
+# RX answer (rx_reply_build -> rx_neigh_updates -> rx_neigh_build -> neigh_apply
+# as one call: two launches where each list has at most RX_ANSWER_SMALL entries).
+
+RX_ANSWER_SMALL = 4096  # WC_RX_ANSWER_SMALL
+RX_ANSWER_SMALL_APPLY = 1024  # WC_RX_ANSWER_SMALL_APPLY: u_m where a table is given
+
+
+class RxAnswer(NamedTuple):
+    """The outputs of rx_answer."""
+    reply_lens: torch.Tensor    # uint16, r_m: 0 where no reply was written
+    reply_built: torch.Tensor   # 1 int64, written
+    neigh_lens: torch.Tensor    # uint16, n_m
+    neigh_built: torch.Tensor   # 1 int64, written
+    updates: torch.Tensor       # (u_m, 24) uint8: struct wc_neigh_update
+    dropped: Optional[torch.Tensor]  # 1 int64, accumulated; None without a table
+
+
+class _AnswerIo(ctypes.Structure):  # struct wc_rx_answer_io
+    _fields_ = [("action", ctypes.c_void_p), ("rlist", ctypes.c_void_p),
+                ("rcount", ctypes.c_void_p), ("nact", ctypes.c_void_p),
+                ("nrlist", ctypes.c_void_p), ("nrcount", ctypes.c_void_p),
+                ("ulist", ctypes.c_void_p), ("ucount", ctypes.c_void_p),
+                ("r_out_base", ctypes.c_void_p), ("r_out_off", ctypes.c_void_p),
+                ("r_m", ctypes.c_uint32), ("ip_id", ctypes.c_void_p),
+                ("r_out_len", ctypes.c_void_p), ("r_built", ctypes.c_void_p),
+                ("n_out_base", ctypes.c_void_p), ("n_out_off", ctypes.c_void_p),
+                ("n_m", ctypes.c_uint32), ("n_out_len", ctypes.c_void_p),
+                ("n_built", ctypes.c_void_p), ("u_m", ctypes.c_uint32),
+                ("upd", ctypes.c_void_p), ("tab", ctypes.c_void_p),
+                ("dropped", ctypes.c_void_p)]
+
+
+def rx_answer_scratch(u_m: int) -> int:
+    """Bytes of device scratch wc_rx_answer needs for u_m update records when a
+    table is given (no GPU)."""
+    return int(_lib.active().wc_rx_answer_scratch(int(u_m)))
+
+
+def rx_answer(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor,
+              plan, engine: torch.Tensor, reply_out: torch.Tensor, reply_offsets: torch.Tensor,
+              neigh_out: torch.Tensor, neigh_offsets: torch.Tensor, u_m: int,
+              slot_bytes: int = 2048, ip_ids: Optional[torch.Tensor] = None,
+              tab: Optional[torch.Tensor] = None, out: Optional[RxAnswer] = None,
+              scratch: Optional[torch.Tensor] = None, stream=None,
+              check: bool = True) -> RxAnswer:
+    """Everything behind a drain in one call (wc_rx_answer): the outputs of
+    rx_reply_build (``reply_out`` / ``reply_offsets`` / ``ip_ids``),
+    rx_neigh_updates (``u_m`` records), rx_neigh_build (``neigh_out`` /
+    ``neigh_offsets``) and, where ``tab`` is given, neigh_apply on it, byte for
+    byte -- two launches where the two offset arrays and ``u_m`` are at most
+    ``RX_ANSWER_SMALL`` (``u_m`` at most ``RX_ANSWER_SMALL_APPLY`` with a table),
+    the four calls above that.  ``plan``: an ``RxDrain``, or
+    the eight tensors ``(actions, reply_list, reply_count, nact,
+    neigh_reply_list, neigh_reply_count, update_list, update_count)``.  The reply
+    slots and the neighbour slots must not overlap each other.  Returns an
+    ``RxAnswer``; both built counts are written, ``dropped`` is accumulated
+    (zero in a tuple allocated here).  ``out``: an earlier call's ``RxAnswer`` to
+    write into again; ``scratch``: ``rx_answer_scratch(u_m)`` bytes, allocated
+    here unless given -- give both per call in flight when ``stream`` is not the
+    current stream.  Asynchronous; calls on one table are ordered by the
+    caller."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
+    d = base.device
+    if isinstance(plan, RxDrain):
+        plan = (plan.actions, plan.reply_list, plan.reply_count, plan.nact,
+                plan.neigh_reply_list, plan.neigh_reply_count, plan.update_list,
+                plan.update_count)
+    if not isinstance(plan, (tuple, list)) or len(plan) != 8:
+        raise ValueError("plan must be an RxDrain or its eight tensors (actions, reply_list, "
+                         "reply_count, nact, neigh_reply_list, neigh_reply_count, update_list, "
+                         "update_count)")
+    actions, rlist, rcount, nact, nrlist, nrcount, ulist, ucount = plan
+    r_m, r_lens, r_built = _build_args("rx_reply_plan", base, n, "actions", actions, rlist, rcount,
+                                       engine, reply_out, reply_offsets, slot_bytes, check, ip_ids)
+    n_m, n_lens, n_built = _build_args("rx_neigh_plan", base, n, "nact", nact, nrlist, nrcount,
+                                       engine, neigh_out, neigh_offsets, slot_bytes, check)
+    u_m = int(u_m)
+    if not 0 <= u_m <= (0xFFFFFFFF if tab is None else _NEIGH_APPLY_MAX):
+        raise ValueError("u_m is a uint32, and at most 2^31 with a table")
+    _list_args("update_list", "rx_neigh_plan", ulist, ucount, u_m, n, d)
+    if tab is not None:
+        _neigh_tab(tab)
+        if tab.device != d:
+            raise ValueError(f"tab is on {tab.device}, base on {d}")
+    if out is None:
+        out = RxAnswer(r_lens, r_built, n_lens, n_built,
+                       torch.empty((u_m, NEIGH_UPDATE.itemsize), dtype=torch.uint8, device=d),
+                       _bad_counter(None, d) if tab is not None else None)
+    else:
+        if not isinstance(out, RxAnswer):
+            raise ValueError("out must be an RxAnswer (an earlier call's result)")
+        _byte_array("reply_lens", out.reply_lens, r_m, d, 2)
+        _byte_array("neigh_lens", out.neigh_lens, n_m, d, 2)
+        _byte_array("reply_built", out.reply_built, 1, d, 8)
+        _byte_array("neigh_built", out.neigh_built, 1, d, 8)
+        if not isinstance(out.updates, torch.Tensor) or out.updates.device != d \
+                or not out.updates.is_contiguous() \
+                or _nbytes(out.updates) < u_m * NEIGH_UPDATE.itemsize:
+            raise ValueError(f"updates must be contiguous (u_m, 24) bytes on {d}")
+        if tab is not None:
+            out = out._replace(dropped=_bad_counter(out.dropped, d, "dropped"))
+    need = rx_answer_scratch(u_m) if tab is not None else 0
+    if scratch is None:
+        scratch = _scratch(need, d)
+    elif _nbytes(scratch) < need or scratch.device != d:
+        raise ValueError(f"scratch must hold rx_answer_scratch(u_m) bytes on {d}")
+
+    def ptr(t, some=True):
+        return t.data_ptr() if t is not None and some else None
+    io = _AnswerIo(ptr(actions), ptr(rlist), ptr(rcount), ptr(nact), ptr(nrlist), ptr(nrcount),
+                   ptr(ulist), ptr(ucount),
+                   ptr(reply_out), ptr(reply_offsets, r_m), r_m, ptr(ip_ids, r_m),
+                   ptr(out.reply_lens, r_m), ptr(out.reply_built),
+                   ptr(neigh_out), ptr(neigh_offsets, n_m), n_m, ptr(out.neigh_lens, n_m),
+                   ptr(out.neigh_built), u_m, ptr(out.updates, u_m), ptr(tab),
+                   ptr(out.dropped, tab is not None))
+    with _on_device(d):
+        _check("wc_rx_answer", _lib.active().wc_rx_answer(
+            _dev_ptr(base), _dev_ptr(offsets), _dev_ptr(frame_lens), n, engine.data_ptr(),
+            int(slot_bytes), ctypes.byref(io), scratch.data_ptr(), _stream_ptr(stream, d)))
+    return out
+
+
+# --------------------------------------------------------------------------
 # TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
 
 # enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)

@@ -374,6 +374,51 @@ hipError_t launch_tx_build_gated(void *base, const uint64_t *offs, const void *d
                                  uint16_t *frame_len, uint8_t *status, uint16_t *out_ip,
                                  uint16_t *out_udp, uint64_t *errors, bool nt, hipStream_t st);
 
+// RX answer (wc_k_rxanswer.hip): for at most ra::kSmall entries in each of the
+// three lists, every output of launch_rx_reply_build, launch_rx_neigh_updates,
+// launch_rx_neigh_build and launch_neigh_apply, from two launches and with no
+// memset in front: launch_rx_answer_frames, one grid whose workgroups are
+// split between the three list kernels' bodies (wc_rx_answer.h; it writes
+// neither built count, and with n = 0 zero lengths and zero records), and
+// launch_rx_answer_apply, one workgroup that counts the stored lengths into
+// *r_built and *n_built (written, not accumulated) and, where tab is given and
+// u_m > 0, applies the records with its entry indices in LDS.  A part with m =
+// 0 has none of its pointers looked at but its built count.
+struct RxAnswerArgs {
+    const uint8_t *base;
+    const uint64_t *offs;
+    const uint16_t *flens;
+    uint64_t n;
+    const uint32_t *eng;
+    uint32_t slot_bytes;
+    const uint8_t *action;
+    const uint32_t *rlist;
+    const uint64_t *rcount;
+    const uint8_t *nact;
+    const uint32_t *nrlist;
+    const uint64_t *nrcount;
+    const uint32_t *ulist;
+    const uint64_t *ucount;
+    uint8_t *r_out_base;
+    const uint64_t *r_out_off;
+    uint32_t r_m;
+    const uint16_t *ip_id;
+    uint16_t *r_out_len;
+    uint64_t *r_built;
+    uint8_t *n_out_base;
+    const uint64_t *n_out_off;
+    uint32_t n_m;
+    uint16_t *n_out_len;
+    uint64_t *n_built;
+    uint32_t u_m;
+    uint32_t *upd;
+    uint32_t *tab;
+    uint64_t *dropped;
+};
+// (no launch where all three m are 0)
+hipError_t launch_rx_answer_frames(const RxAnswerArgs &a, int cus, hipStream_t st);
+hipError_t launch_rx_answer_apply(const RxAnswerArgs &a, hipStream_t st);
+
 // Resident small-batch server (wc_k_serve.hip).  Host-mapped pinned memory:
 // one record per packet, written by the host (seq last), polled / read by the
 // server's waves; one result slot per packet, written by the GPU in one

@@ -605,6 +605,29 @@ struct GlobalMem {
     }
 };
 
+// wc_tx_neigh.h's Words on the device, over words in global memory
+// (wc_k_txneigh.hip, wc_k_rxanswer.hip): what lanes tell each other goes
+// through the atomics and is read back with agent-scope loads.
+struct DevWords {
+    __device__ __forceinline__ uint32_t ld(const uint32_t *p) const { return *p; }
+    __device__ __forceinline__ uint32_t ld_now(const uint32_t *p) const
+    {
+        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ uint32_t ld8(const uint8_t *p) const { return *p; }
+    __device__ __forceinline__ void st(uint32_t *p, uint32_t v) const { *p = v; }
+    __device__ __forceinline__ void st16(uint32_t *p, uint32_t v) const
+    {
+        *reinterpret_cast<uint16_t *>(p) = (uint16_t)v;
+    }
+    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *p = (uint8_t)v; }
+    __device__ __forceinline__ uint32_t cas(uint32_t *p, uint32_t expect, uint32_t want) const
+    {
+        return atomicCAS(p, expect, want);
+    }
+    __device__ __forceinline__ void amax(uint32_t *p, uint32_t v) const { atomicMax(p, v); }
+};
+
 // ---------------------------------------------------------------------------
 // The list kernels' frame (k_rx_reply_build, k_rx_neigh_updates,
 // k_rx_neigh_build): entry j < MIN(*count, m) of a device list names a frame,

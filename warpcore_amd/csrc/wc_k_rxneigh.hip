@@ -32,8 +32,7 @@
 // words cannot wrap a uint32.  The only atomic is the built count's, one per
 // workgroup with a built reply.
 // Roofline: latency -- a few dependent loads per frame, a few cache lines each.
-#include "wc_rx_hdr.h"
-#include "wc_rx_neigh.h"
+#include "wc_rx_build.h"
 
 namespace wc {
 namespace {
@@ -103,24 +102,10 @@ k_rx_neigh_updates(const uint8_t *__restrict__ base, const uint64_t *__restrict_
                    const unsigned long long *__restrict__ count, uint32_t m,
                    uint32_t *__restrict__ upd)
 {
-    const uint64_t lim = list_limit(count, m);
-    const GlobalMem mem{};
-    const uint64_t S = (uint64_t)gridDim.x * kNeighBlock;
-    uint64_t j = (uint64_t)blockIdx.x * kNeighBlock + threadIdx.x;
-    ListMeta cur = list_meta(list_entry(list, j, lim), n, nact, offs, flens);
-    uint64_t idx_n = list_entry(list, j + S, lim);
-    for (; j < m; j += S) {
-        const ListMeta nxt = list_meta(idx_n, n, nact, offs, flens);
-        idx_n = list_entry(list, j + 2 * S, lim);
-        uint32_t u[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-        if (cur.live && rn::is_update(cur.act))
-            rn::record_of(mem, (uint64_t)(uintptr_t)base + cur.off, cur.flen, cur.act, u);
-        uint32_t *o = upd + 6u * j;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            o[k] = u[k];
-        cur = nxt;
-    }
+    // (the bodies of both: wc_rx_build.h, shared with k_rx_answer_frames)
+    rx_neigh_updates_body(base, offs, flens, n, nact, list, count, m, upd,
+                          (uint64_t)blockIdx.x * kNeighBlock + threadIdx.x,
+                          (uint64_t)gridDim.x * kNeighBlock);
 }
 
 __global__ void __launch_bounds__(kNeighBlock)
@@ -132,28 +117,10 @@ k_rx_neigh_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
                  uint32_t slot_bytes, uint16_t *__restrict__ out_len,
                  unsigned long long *__restrict__ built)
 {
-    const uint64_t lim = list_limit(count, m);
-    const GlobalMem mem{};
-    uint32_t nbuilt = 0;
-    const uint64_t S = (uint64_t)gridDim.x * kNeighBlock;
-    uint64_t j = (uint64_t)blockIdx.x * kNeighBlock + threadIdx.x;
-    ListMeta cur = list_meta(list_entry(list, j, lim), n, nact, offs, flens);
-    uint64_t ooff = j < m ? out_off[j] : 0u;
-    uint64_t idx_n = list_entry(list, j + S, lim);
-    for (; j < m; j += S) {
-        const ListMeta nxt = list_meta(idx_n, n, nact, offs, flens);
-        const uint64_t ooff_n = j + S < m ? out_off[j + S] : 0u;
-        idx_n = list_entry(list, j + 2 * S, lim);
-        uint32_t len = 0;
-        if (cur.live && rn::is_reply(cur.act))
-            len = rn::build(mem, (uint64_t)(uintptr_t)base + cur.off, cur.flen, cur.act, eng,
-                            (uint64_t)(uintptr_t)out_base + ooff, slot_bytes);
-        out_len[j] = (uint16_t)len;
-        nbuilt += len != 0u;
-        cur = nxt;
-        ooff = ooff_n;
-    }
-    block_count_add<kNeighBlock / 64>(group_sum<64>(nbuilt), built);
+    rx_neigh_build_body<kNeighBlock / 64, true>(base, offs, flens, n, nact, list, count, eng,
+                                                out_base, out_off, m, slot_bytes, out_len, built,
+                                                (uint64_t)blockIdx.x * kNeighBlock + threadIdx.x,
+                                                (uint64_t)gridDim.x * kNeighBlock);
 }
 
 } // namespace

@@ -57,25 +57,10 @@
 // (as many workgroups as the device holds at once).
 // Roofline: HBM -- the ICMP bytes once in the plan, once more (L2-warm behind
 // the plan) in the build, the replies written once.
-#include "wc_rx_hdr.h"
-#include "wc_rx_reply.h"
+#include "wc_rx_build.h"
 
 namespace wc {
 namespace {
-
-typedef u32x4 __attribute__((address_space(1))) *gst128_ptr;
-
-struct ReplyMem : GlobalMem { // and rr::copy_chunk's accesses on rr::Quad
-    __device__ __forceinline__ rr::Quad ld128(uint64_t a) const
-    {
-        const u32x4 v = load_chunk<false>(a);
-        return rr::Quad{v.x, v.y, v.z, v.w};
-    }
-    __device__ __forceinline__ void st128(uint64_t a, const rr::Quad &q) const
-    {
-        *(gst128_ptr)(uintptr_t)a = u32x4{q.x, q.y, q.z, q.w};
-    }
-};
 
 constexpr int kRrSpan = 15; // XCD super-blocks of 2^15 tiles, as the RX verdict's
 
@@ -195,74 +180,12 @@ k_rx_reply_build(const uint8_t *__restrict__ base, const uint64_t *__restrict__ 
                  uint32_t slot_bytes, const uint16_t *__restrict__ ip_id,
                  uint16_t *__restrict__ out_len, unsigned long long *__restrict__ built)
 {
-    const int lane = threadIdx.x & 63;
+    // (rx_reply_build_body, wc_rx_build.h: shared with k_rx_answer_frames)
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t lim = list_limit(count, m);
-    const uint32_t mtu = rr::eng_mtu(eng);
-    const ReplyMem mem{};
-    uint32_t nbuilt = 0; // wave-uniform
-
-    // A wave's replies are j, j + S, ...; each costs two dependent load rounds
-    // in front of its stores (the frame's length fields; then its addresses and
-    // data), because the two rounds in front of those -- the list entry, then
-    // what it names -- are issued one and two replies ahead, beside the loads
-    // of the reply being built.
-    const uint64_t S = (uint64_t)gridDim.x * kBuildWaves;
-    uint64_t j = (uint64_t)blockIdx.x * kBuildWaves + w;
-    // (the slot and ip->id of reply j are read one reply ahead too)
-    auto slot_of = [&](uint64_t k) { return k < m ? out_off[k] : 0u; };
-    auto ipid_of = [&](uint64_t k) { return ip_id && k < m ? (uint32_t)ip_id[k] : 0u; };
-    ListMeta cur = list_meta(list_entry(list, j, lim), n, action, offs, flens);
-    uint64_t ooff = slot_of(j);
-    uint32_t ipid = ipid_of(j);
-    uint64_t idx_n = list_entry(list, j + S, lim);
-    for (; j < m; j += S) {
-        const ListMeta nxt = list_meta(idx_n, n, action, offs, flens);
-        const uint64_t ooff_n = slot_of(j + S);
-        const uint32_t ipid_n = ipid_of(j + S);
-        idx_n = list_entry(list, j + 2 * S, lim);
-        uint32_t len = 0;
-        if (cur.live && rr::is_reply(cur.act)) { // (wave-uniform branches throughout)
-            const uint32_t act = cur.act, flen = cur.flen;
-            const uint64_t fa = (uint64_t)(uintptr_t)base + cur.off;
-            const uint64_t fend = fa + flen;
-            // vhl, tos, ip->len (IPv4) and ip6->len: frame bytes 14..17, 18..19
-            const uint32_t g0 = rr::frame_dword(mem, fa, fend, 14u);
-            const uint32_t g1 = rr::frame_dword(mem, fa, fend, 18u);
-            const bool v4 = rr::reply_v4(act);
-            const uint32_t hl = v4 ? ((g0 & 15u) * 4u) : 40u;
-            const uint32_t ip_len = txb::bswap16(v4 ? g0 >> 16 : g1);
-            const rr::Reply r = rr::reply_of(act, hl, ip_len, flen, mtu, slot_bytes);
-            if (rr::is_reply(r.action)) {
-                const rr::Req q = rr::request_of(mem, fa, fend, act, hl);
-                const uint64_t da = (uint64_t)(uintptr_t)out_base + ooff;
-                const uint64_t dd = da + (v4 ? 42u : 62u), sa = fa + r.s0;
-                const uint32_t nd = rr::copy_dwords(dd, r.dlen);
-                const rr::Chunks ch = rr::copy_chunks(dd, r.dlen);
-                uint32_t acc = 0;
-                for (uint32_t c = ch.c0 + (uint32_t)lane; c < ch.c1; c += 64u)
-                    acc += rr::copy_chunk(mem, sa, dd, c);
-                // the dwords in front of and behind the whole chunks: at most 4 + 4
-                const uint32_t i = (uint32_t)lane < ch.i0 ? (uint32_t)lane
-                                                          : ch.i1 + ((uint32_t)lane - ch.i0);
-                if (i < nd)
-                    acc += rr::copy_dword(mem, sa, dd, r.dlen, i);
-                const uint32_t data = rr::fold16(group_sum<64>(acc));
-                uint32_t h[16];
-                rr::headers(r, q, eng, ipid, data, h);
-                if (lane == 0)
-                    txb::store_headers(mem, da, v4, h);
-                len = r.len;
-            }
-        }
-        if (lane == 0)
-            out_len[j] = (uint16_t)len;
-        nbuilt += len != 0u;
-        cur = nxt;
-        ooff = ooff_n;
-        ipid = ipid_n;
-    }
-    block_count_add<kBuildWaves>(nbuilt, built);
+    rx_reply_build_body<kBuildWaves, true>(base, offs, flens, n, action, list, count, eng, out_base,
+                                           out_off, m, slot_bytes, ip_id, out_len, built,
+                                           (uint64_t)blockIdx.x * kBuildWaves + w,
+                                           (uint64_t)gridDim.x * kBuildWaves);
 }
 
 } // namespace

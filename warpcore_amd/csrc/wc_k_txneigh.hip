@@ -37,26 +37,7 @@ namespace {
 
 constexpr uint32_t kTnBlock = 256;
 
-// wc_tx_neigh.h's Words on the device.
-struct DevWords {
-    __device__ __forceinline__ uint32_t ld(const uint32_t *p) const { return *p; }
-    __device__ __forceinline__ uint32_t ld_now(const uint32_t *p) const
-    {
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __device__ __forceinline__ uint32_t ld8(const uint8_t *p) const { return *p; }
-    __device__ __forceinline__ void st(uint32_t *p, uint32_t v) const { *p = v; }
-    __device__ __forceinline__ void st16(uint32_t *p, uint32_t v) const
-    {
-        *reinterpret_cast<uint16_t *>(p) = (uint16_t)v;
-    }
-    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *p = (uint8_t)v; }
-    __device__ __forceinline__ uint32_t cas(uint32_t *p, uint32_t expect, uint32_t want) const
-    {
-        return atomicCAS(p, expect, want);
-    }
-    __device__ __forceinline__ void amax(uint32_t *p, uint32_t v) const { atomicMax(p, v); }
-};
+// (wc_tx_neigh.h's Words on the device: DevWords, wc_device.h)
 
 __global__ void __launch_bounds__(kTnBlock)
 k_neigh_tab_init(uint32_t *__restrict__ tab, uint32_t cap)

@@ -437,6 +437,37 @@ inline bool rx_scratch_ok(bool lists, const void *d_scratch)
     return !lists || (d_scratch && !((uintptr_t)d_scratch & 3u));
 }
 
+// The pointer rules of the calls behind a plan, each stated once: the call
+// itself and wc_rx_answer (wc_rt_rxanswer.cpp) refuse the same.
+// wc_rx_reply_build / wc_rx_neigh_build, m > 0 and n > 0 (rx_list_build's
+// `ptrs`): every pointer the launch reads is given, the table 4-byte aligned.
+inline bool rx_build_ptrs_ok(const void *d_base, const void *d_off, const void *d_frame_len,
+                             const void *d_code, const void *d_list, const void *d_count,
+                             const void *d_eng, const void *d_out_base, const void *d_out_off)
+{
+    return d_base && d_off && d_frame_len && d_code && d_list && d_count && d_eng &&
+           !((uintptr_t)d_eng & 3u) && d_out_base && d_out_off;
+}
+
+// wc_rx_neigh_updates, m > 0: the records; and with n > 0 what the launch reads.
+inline bool rx_updates_ptrs_ok(const void *d_base, const void *d_off, const void *d_frame_len,
+                               uint64_t n, const void *d_nact, const void *d_list,
+                               const void *d_count, const void *d_upd)
+{
+    if (!d_upd || ((uintptr_t)d_upd & 3u))
+        return false;
+    return n == 0 || (d_base && d_off && d_frame_len && d_nact && d_list && d_count);
+}
+
+// wc_neigh_apply, m > 0 (wc_rt_txneigh.cpp; 2^31 is tn::kApplyMax).
+inline bool neigh_apply_args_ok(const void *d_tab, const void *d_upd, const void *d_count,
+                                uint32_t m, const void *d_scratch)
+{
+    if (m > (1u << 31) || !d_tab || !d_upd || !d_count || !d_scratch)
+        return false;
+    return !(((uintptr_t)d_tab & 15u) || ((uintptr_t)d_upd & 3u) || ((uintptr_t)d_scratch & 3u));
+}
+
 // wc_rx_reply_build / wc_rx_neigh_build around their one launch: the argument
 // checks in their order (ptrs: every pointer a call with m != 0 and n != 0
 // reads is given, the table 4-byte aligned), *d_built zeroed -- the launch's

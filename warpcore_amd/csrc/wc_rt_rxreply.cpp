@@ -66,8 +66,8 @@ int wc_rx_reply_build(const void *d_base, const uint64_t *d_off, const uint16_t 
                       const uint64_t *d_out_off, uint32_t m, uint32_t slot_bytes,
                       const uint16_t *d_ip_id, uint16_t *d_out_len, uint64_t *d_built, void *stream)
 {
-    const bool ptrs = d_base && d_off && d_frame_len && d_action && d_list && d_count && d_eng &&
-                      !((uintptr_t)d_eng & 3u) && d_out_base && d_out_off;
+    const bool ptrs = rx_build_ptrs_ok(d_base, d_off, d_frame_len, d_action, d_list, d_count, d_eng,
+                                       d_out_base, d_out_off);
     return rx_list_build(n, m, slot_bytes, ptrs, d_out_len, d_built, (hipStream_t)stream, [&](int cus) {
         return wc::launch_rx_reply_build(d_base, d_off, d_frame_len, n, d_action, d_list, d_count,
                                          d_eng, d_out_base, d_out_off, m, slot_bytes, d_ip_id,

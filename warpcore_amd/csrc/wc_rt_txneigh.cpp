@@ -26,6 +26,7 @@ static_assert(sizeof(struct wc_neigh_update) == 4 * tn::kUpdWords &&
                   sizeof(struct wc_tx_sock) == 4 * wc::txb::kSockWords,
               "the records and entries as dwords");
 static_assert(tn::kResolveMax == 65536u, "the TX build's ndst limit");
+static_assert(tn::kApplyMax == 1u << 31, "neigh_apply_args_ok's limit");
 
 namespace {
 
@@ -68,9 +69,7 @@ int wc_neigh_apply(void *d_tab, const struct wc_neigh_update *d_upd, const uint6
 {
     if (m == 0)
         return WC_OK;
-    if (m > tn::kApplyMax || !d_tab || !d_upd || !d_count || !d_scratch)
-        return WC_EINVAL;
-    if (((uintptr_t)d_tab & 15u) || ((uintptr_t)d_upd & 3u) || ((uintptr_t)d_scratch & 3u))
+    if (!neigh_apply_args_ok(d_tab, d_upd, d_count, m, d_scratch))
         return WC_EINVAL;
     Ready R;
     if (R.rc)
