@@ -852,6 +852,125 @@ int wc_rx_answer(const void *d_base, const uint64_t *d_off, const uint16_t *d_fr
                  const struct wc_rx_engine *d_eng, uint32_t slot_bytes,
                  const struct wc_rx_answer_io *io /* host struct */, void *d_scratch, void *stream);
 
+/* --- RX echo: delivered datagrams become a TX batch on the device ---------- */
+
+/* The reference's own server application (bin/inetd.c:161-169): port 7 hands
+ * every received iov back to w_tx -- sq_concat(&o, &i); w_tx(s, &o) -- with the
+ * address, port and TOS udp_rx left in it (udp.c:107-110, 141), and udp_tx
+ * writes the headers in front of v->buf; port 9 discards.  The drain ends with
+ * each socket's delivered frames as a run of list / start and a wc_rx_record
+ * per frame; the pump begins with a wc_tx_desc per frame, a wc_tx_dst / d_af
+ * table and payloads behind their header space.  wc_rx_echo gets from the
+ * first to the second in ONE launch for every n and m, so that the ping /
+ * inetd pair is wc_rx_drain -> wc_rx_answer -> wc_rx_echo -> wc_tx_pump on one
+ * stream with no host read.
+ *
+ * Inputs.  d_rec (n records), d_list (n entries) and d_start (256) are what
+ * wc_rx_drain or wc_rx_demux left.  d_map has ns entries (ns <= 254): a value
+ * <= 255 is the wc_tx_sock index RX socket s answers from, any value above 255
+ * (WC_ECHO_OFF) means the socket is not echoed.  The unbound run (start[254 ..
+ * 255]) is never echoed.
+ *
+ * Echo order.  Sockets ascending, each socket's run in ring order (inetd.c's
+ * sl_foreach / w_rx / w_tx, one socket after another): entry j is the j-th
+ * frame of the concatenated runs of the switched-on sockets.  A run is
+ * [start[s], start[s+1]) and counts as empty unless start[s] <= start[s+1] <=
+ * n, so stale starts are harmless.  E is the total; *count = E is written, not
+ * accumulated.  Entries j >= m are dropped: the caller sees E > m.
+ *
+ * Entry j < min(E, m), from frame i = the list entry, gets status[j]; the
+ * first rule that holds names it:
+ *   WC_EC_STALE    i >= n, the record's af is not 4 / 6, or the record is none a
+ *                  delivery writes for a frame of d_frame_len[i] bytes: hl
+ *                  below hl_tx, data_off not 14 + hl + 8, or the source
+ *                  address not inside the frame
+ *   WC_EC_SHORT    data_off + data_len > frame_len (the record's documented
+ *                  OK_NO_CKSUM case)
+ *   WC_EC_NO_ROOM  copy mode and 14 + hl_tx + 8 + data_len > out_slot_bytes
+ *   WC_EC_ECHO     otherwise; then, with hl_tx = 20 for af 4 and 40 for af 6:
+ *     desc[j] = { data_len = rec.data_len, ip_id = d_ip_id ? d_ip_id[j] : 0,
+ *                 sock = (uint8_t)d_map[s], tos = rec.tos, dst = j } -- udp_tx
+ *       reading v->len / v->flags; the IP id stays the caller's random draw, as
+ *       in wc_rx_reply_build.
+ *     dsts[j] = { addr = the frame's IP source at rec.src_off (af 4: 4 bytes
+ *       and 12 zero bytes; af 6: 16 bytes), port = rec.sport as stored, dmac =
+ *       frame bytes 6..11 }.  af[j] = rec.af.
+ *       Deliberate difference 1: dmac, the sender's Ethernet source, is a
+ *       PLACEHOLDER.  The reference asks who_has for every send, and so does
+ *       wc_tx_pump, whose resolve overwrites the six bytes of every entry; only
+ *       a caller that hands the batch to wc_tx_build_ragged directly sends to
+ *       the placeholder.
+ *     Copy mode (d_out_base and d_out_off given, out->tx_off NULL): the
+ *       data_len payload bytes are copied to d_out_base + d_out_off[j] + 14 +
+ *       hl_tx + 8, where wc_tx_build_ragged expects them; nothing else of the
+ *       slot is written.  No byte outside [frame, frame + frame_len) is USED;
+ *       bytes are LOADED as the aligned 16-byte chunks and dwords that overlap
+ *       the payload (here and for the address and MAC fields in both modes),
+ *       so a load can take up to 15 bytes in front of the frame or behind its
+ *       end -- never outside the aligned 16-byte chunks that overlap the frame.
+ *       The RX buffer must therefore be readable up to the next 16-byte
+ *       boundary behind its last frame, as for every RX call of this library
+ *       (any device allocation is).
+ *       The slots must not overlap each other or the RX buffer.
+ *     In-place mode (d_out_base and d_out_off NULL, out->tx_off given): no
+ *       payload byte is read or written; tx_off[j] = d_off[i] + (rec.hl -
+ *       hl_tx), so that the pump, called with d_base and tx_off, writes its
+ *       headers directly in front of the received payload -- the reference's
+ *       zero-copy echo.
+ *       Deliberate difference 2: for an IPv4 frame with options (hl > 20) the
+ *       reference builds at v->base and would send the option bytes as
+ *       payload; the echo shifts the frame start instead.  The built frame
+ *       starts up to 40 bytes into the RX slot, so the caller passes the pump a
+ *       slot_bytes reduced by the largest shift, 40.
+ *   src[j] (optional) = i wherever i < n, else 0xFFFFFFFF.
+ * Exactly one of the two modes must be selected (with m > 0).
+ *
+ * Inert entries -- every j in [min(E, m), m) (WC_EC_NONE, src 0xFFFFFFFF) and
+ * every SHORT / NO_ROOM / STALE entry -- are written so that any later build
+ * or pump refuses them without touching a slot: desc = { data_len 0xFFFF,
+ * ip_id 0, sock 0, tos 0, dst = j } (the build's check 3: WC_TX_MALFORMED, the
+ * frame untouched), dsts[j] all zero and af[j] = 0 (resolve: WC_NR_BAD_AF),
+ * tx_off[j] = 0, nothing copied.  All m entries of every array are therefore
+ * always written, as wc_rx_answer does for its records: the caller calls the
+ * pump with n = ndst = m and never reads E.  The inert entries count in the
+ * pump's *errors; status tells them apart.  *skipped (optional, accumulated)
+ * grows by the SHORT + NO_ROOM + STALE entries below m.
+ *
+ * m = 0 is WC_OK: it writes *count and looks at no other output.  n = 0 or ns
+ * = 0 gives E = 0 and m inert entries, and looks at no RX pointer (d_base,
+ * d_off, d_frame_len, d_rec, d_list, d_start and d_map may be NULL).
+ * WC_EINVAL, before a device is touched: a NULL out or count; n > 2^32, ns >
+ * 254, m > WC_RX_ECHO_MAX or out_slot_bytes > 65535; with m > 0 a NULL desc /
+ * dsts / af / status, both modes or neither; desc not 8-byte aligned, dsts not
+ * 4-byte aligned, d_rec not 16-byte aligned, tx_off / d_out_off not 8-byte
+ * aligned; with n > 0 and ns > 0 a NULL d_base / d_off / d_frame_len / d_rec /
+ * d_list / d_start / d_map.  Asynchronous on `stream`, no library lock, no
+ * scratch.  The one launch: no workgroup waits for another, nothing spins, the
+ * only atomic is *skipped's (one per wave with a skipped entry), all global
+ * stores are plain vector stores, and the same input gives the same output. */
+enum wc_rx_echo_status {   /* uint8, all < 32 so wc_rx_select masks apply */
+    WC_EC_ECHO    = 0,     /* descriptor, destination and payload are ready for the pump */
+    WC_EC_NONE    = 4,     /* j at or past the echo count: padding */
+    WC_EC_SHORT   = 8,     /* data_off + data_len > frame_len: nothing is read past the frame */
+    WC_EC_NO_ROOM = 9,     /* copy mode: 14 + hl_tx + 8 + data_len > out_slot_bytes */
+    WC_EC_STALE   = 10,    /* list index >= n, or a record no delivery wrote for the frame */
+};
+#define WC_ECHO_OFF 0xFFFFu        /* d_map[s]: socket s is not echoed (inetd's discard) */
+#define WC_RX_ECHO_MAX 65536u      /* m: wc_tx_desc.dst is 16 bits, the build's ndst limit */
+
+struct wc_rx_echo_out {            /* host struct of device pointers, m entries each */
+    struct wc_tx_desc *desc; struct wc_tx_dst *dsts; uint8_t *af;
+    uint8_t *status; uint32_t *src /* optional: the ring index i of entry j */;
+    uint64_t *tx_off  /* in-place mode only */;
+    uint64_t *count   /* written: E, the number of echo frames found */;
+    uint64_t *skipped /* optional, accumulated: SHORT + NO_ROOM + STALE entries below m */;
+};
+int wc_rx_echo(const void *d_base, const uint64_t *d_off, const uint16_t *d_frame_len, uint64_t n,
+               const struct wc_rx_record *d_rec, const uint32_t *d_list, const uint64_t *d_start,
+               const uint16_t *d_map, uint32_t ns, const uint16_t *d_ip_id /* optional, m */,
+               void *d_out_base, const uint64_t *d_out_off, uint32_t out_slot_bytes, uint32_t m,
+               const struct wc_rx_echo_out *out /* host struct */, void *stream);
+
 /* --- TX neighbours: device neighbour cache, batched who_has, solicitations - */
 
 /* What lies between "RX produces update records" and "TX consumes destination

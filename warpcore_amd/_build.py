@@ -47,7 +47,7 @@ HIP_SOURCES = [CSRC / "wc_k_strided.hip", CSRC / "wc_k_lean.hip", CSRC / "wc_k_s
                CSRC / "wc_k_flat.hip",
                CSRC / "wc_k_rx.hip", CSRC / "wc_k_rxsel.hip", CSRC / "wc_k_rxdemux.hip",
                CSRC / "wc_k_rxreply.hip", CSRC / "wc_k_rxneigh.hip", CSRC / "wc_k_rxdrain.hip",
-               CSRC / "wc_k_rxanswer.hip",
+               CSRC / "wc_k_rxanswer.hip", CSRC / "wc_k_rxecho.hip",
                CSRC / "wc_k_tx.hip", CSRC / "wc_k_txbuild.hip", CSRC / "wc_k_txneigh.hip",
                CSRC / "wc_k_txpump.hip",
                CSRC / "wc_k_serve.hip",
@@ -55,7 +55,7 @@ HIP_SOURCES = [CSRC / "wc_k_strided.hip", CSRC / "wc_k_lean.hip", CSRC / "wc_k_s
                CSRC / "wc_k_synth.hip",
                CSRC / "wc_rt_config.cpp", CSRC / "wc_rt_plan.cpp", CSRC / "wc_rt_rx.cpp",
                CSRC / "wc_rt_rxreply.cpp", CSRC / "wc_rt_rxneigh.cpp", CSRC / "wc_rt_rxdrain.cpp",
-               CSRC / "wc_rt_rxanswer.cpp",
+               CSRC / "wc_rt_rxanswer.cpp", CSRC / "wc_rt_rxecho.cpp",
                CSRC / "wc_rt_tx.cpp",
                CSRC / "wc_rt_txneigh.cpp", CSRC / "wc_rt_txpump.cpp", CSRC / "wc_rt_server.cpp", CSRC / "wc_rt_host.cpp", CSRC / "wc_rt_multi.cpp"]
 HIP_DEPS = HIP_SOURCES + [CSRC / "wc_cksum_kernels.h", CSRC / "wc_rccl.h", CSRC / "wc_device.h",
@@ -63,7 +63,7 @@ HIP_DEPS = HIP_SOURCES + [CSRC / "wc_cksum_kernels.h", CSRC / "wc_rccl.h", CSRC 
                           CSRC / "wc_flat.h", CSRC / "wc_seg.h", CSRC / "wc_rx_hdr.h",
                           CSRC / "wc_rx_socktab.h", CSRC / "wc_rx_demux.h", CSRC / "wc_tx_build.h", CSRC / "wc_rx_reply.h",
                           CSRC / "wc_rx_neigh.h", CSRC / "wc_tx_neigh.h", CSRC / "wc_tx_pump.h",
-                          CSRC / "wc_rx_build.h", CSRC / "wc_rx_answer.h",
+                          CSRC / "wc_rx_build.h", CSRC / "wc_rx_answer.h", CSRC / "wc_rx_echo.h",
                           INCLUDE / "warpcore_gpu" / "wc_cksum.h"]
 ORACLE_SOURCES = [ORACLE_DIR / "wc_oracle.c", ORACLE_DIR / "wc_oracle.h", ORACLE_DIR / "Makefile"]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",

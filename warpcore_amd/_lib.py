@@ -59,6 +59,8 @@ SIGNATURES = {
     "wc_rx_drain": (_int, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "wc_rx_answer_scratch": (_u64, [_u32]),
     "wc_rx_answer": (_int, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp]),
+    "wc_rx_echo": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32,
+                          _vp, _vp]),
     "wc_neigh_tab_bytes": (_u64, [_u32]),
     "wc_neigh_tab_init": (_int, [_vp, _u32, _vp]),
     "wc_neigh_apply_scratch": (_u64, [_u32]),

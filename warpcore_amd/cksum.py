@@ -1155,6 +1155,156 @@ def rx_answer(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tenso
 
 
 # --------------------------------------------------------------------------
+# RX echo (the delivered datagrams of the switched-on sockets as a TX batch for
+# tx_pump: descriptors, destinations and payloads in one launch).
+
+RX_ECHO_MAX = 65536  # WC_RX_ECHO_MAX
+ECHO_OFF = 0xFFFF    # WC_ECHO_OFF
+EC_ECHO, EC_NONE, EC_SHORT, EC_NO_ROOM, EC_STALE = 0, 4, 8, 9, 10
+EC_NAMES = {EC_ECHO: "echo", EC_NONE: "none", EC_SHORT: "short", EC_NO_ROOM: "no_room",
+            EC_STALE: "stale"}
+EC_MASK_SKIPPED = (1 << EC_SHORT) | (1 << EC_NO_ROOM) | (1 << EC_STALE)
+
+
+class RxEcho(NamedTuple):
+    """The outputs of rx_echo, in struct wc_rx_echo_out's order."""
+    descs: torch.Tensor      # (m, 8) uint8: struct wc_tx_desc
+    dsts: torch.Tensor       # (m, 24) uint8: struct wc_tx_dst
+    af: torch.Tensor         # uint8: 4 / 6, 0 for an inert entry
+    status: torch.Tensor     # uint8 EC_*
+    src: Optional[torch.Tensor]     # uint32: the ring index of entry j, 0xFFFFFFFF without one
+    tx_off: Optional[torch.Tensor]  # int64, in-place mode only: the pump's offsets
+    count: torch.Tensor      # 1 int64, written: E
+    skipped: Optional[torch.Tensor]  # 1 int64, accumulated
+
+
+class _EchoOut(ctypes.Structure):  # struct wc_rx_echo_out
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "desc", "dsts", "af", "status", "src", "tx_off", "count", "skipped")]
+
+
+def _echo_out(out: Optional[RxEcho], m: int, in_place: bool, device) -> RxEcho:
+    """rx_echo's tensors: the caller's, checked, or allocated here."""
+    if out is None:
+        def arr(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=device)
+        return RxEcho(arr((m, 8), torch.uint8), arr((m, 24), torch.uint8), arr(m, torch.uint8),
+                      arr(m, torch.uint8), arr(m, torch.uint32),
+                      arr(m, torch.int64) if in_place else None,
+                      torch.zeros(1, dtype=torch.int64, device=device),
+                      torch.zeros(1, dtype=torch.int64, device=device))
+    if not isinstance(out, RxEcho):
+        raise ValueError("out must be an RxEcho (an earlier call's result)")
+    for name, size in (("descs", 8), ("dsts", 24)):
+        t = getattr(out, name)
+        if not isinstance(t, torch.Tensor) or t.device != device or not t.is_contiguous() \
+                or t.element_size() != 1 or _nbytes(t) < m * size:
+            raise ValueError(f"{name} must be contiguous (m, {size}) bytes on {device}")
+    _byte_array("af", out.af, m, device)
+    _byte_array("status", out.status, m, device)
+    if out.src is not None:
+        _byte_array("src", out.src, m, device, 4)
+    if in_place != (out.tx_off is not None):
+        raise ValueError("tx_off goes with in-place mode alone")
+    if in_place:
+        _byte_array("tx_off", out.tx_off, m, device, 8)
+    _byte_array("count", out.count, 1, device, 8)
+    if out.skipped is not None:
+        _byte_array("skipped", out.skipped, 1, device, 8)
+    return out
+
+
+def rx_echo(base: torch.Tensor, offsets: torch.Tensor, frame_lens: torch.Tensor, plan,
+            echo_map: torch.Tensor, m: Optional[int] = None,
+            out_base: Optional[torch.Tensor] = None, out_offsets: Optional[torch.Tensor] = None,
+            out_slot_bytes: int = 2048, ip_ids: Optional[torch.Tensor] = None,
+            out: Optional[RxEcho] = None, stream=None, check: bool = True) -> RxEcho:
+    """The delivered datagrams of the switched-on sockets as a TX batch
+    (wc_rx_echo, one launch): inetd's port 7 on the device.  ``plan``: an
+    ``RxDrain``, or the three tensors ``(records, list, start)`` of rx_demux;
+    ``echo_map``: one 2-byte entry per RX socket, the ``TX_SOCK`` index it
+    answers from, or ``ECHO_OFF``.  Entry j of the result is the j-th frame of
+    the switched-on sockets' runs, sockets ascending: a descriptor with ``dst =
+    j``, a destination (the frame's IP source and UDP source port; ``dmac`` a
+    placeholder that tx_pump's resolve overwrites), ``af`` and an ``EC_*``
+    status.  Copy mode -- ``out_base`` / ``out_offsets`` given, ``m`` their
+    count: the payloads are copied behind the header space of each slot.
+    In-place mode -- neither given, ``m`` required: ``tx_off`` holds the offsets
+    to hand tx_pump with ``base`` itself, so that it writes its headers in front
+    of the received payloads (pass it a slot length reduced by 40).  All ``m``
+    entries are written (``src`` and ``skipped`` may be None in a tuple handed
+    in), the ones past ``count`` and the skipped ones so that
+    tx_pump refuses them (``TX_MALFORMED``, counted in its ``errors``): call it
+    with all ``m``.  ``count`` is written, ``skipped`` accumulated (zero in a
+    tuple allocated here).  ``ip_ids``: ``m`` uint16, the IPv4 ids as stored.
+    Asynchronous with ``check=False``; under ``check`` (the default) the frame
+    and slot offsets are reduced on the device and read back first, which
+    synchronises -- pass ``check=False`` where drain -> echo -> pump must run
+    with no host read in between.  No scratch."""
+    n = _check_ragged(base, offsets, frame_lens, KIND_IP, check, indexed=True)
+    d = base.device
+    if isinstance(plan, RxDrain):
+        plan = (plan.records, plan.list, plan.start)
+    if not isinstance(plan, (tuple, list)) or len(plan) != 3:
+        raise ValueError("plan must be an RxDrain or the three tensors (records, list, start)")
+    records, lst, start = plan
+    if not isinstance(records, torch.Tensor) or records.device != d or not records.is_contiguous() \
+            or _nbytes(records) < n * RX_RECORD.itemsize:
+        raise ValueError(f"records must be contiguous (n, 16) bytes on {d}")
+    _index_list(lst, n, d)
+    _byte_array("start", start, _RX_STARTS, d, 8)
+    if not isinstance(echo_map, torch.Tensor) or echo_map.device != d \
+            or echo_map.element_size() != 2 or echo_map.is_floating_point() \
+            or not echo_map.is_contiguous() or echo_map.numel() > RX_DEMUX_MAX_SOCKS:
+        raise ValueError(f"echo_map must be at most {RX_DEMUX_MAX_SOCKS} contiguous 2-byte "
+                         f"integers on {d}")
+    ns = echo_map.numel()
+    in_place = out_base is None
+    if (out_base is None) != (out_offsets is None):
+        raise ValueError("out_base and out_offsets go together (neither: in-place mode)")
+    if in_place:
+        if m is None:
+            raise ValueError("in-place mode needs m, the number of entries")
+        m = int(m)
+    else:
+        if not out_base.is_contiguous() or out_base.element_size() != 1 or out_base.device != d:
+            raise ValueError(f"out_base must be a contiguous 1-byte tensor on {d}")
+        if out_offsets.element_size() != 8 or out_offsets.is_floating_point() \
+                or not out_offsets.is_contiguous() or out_offsets.device != d:
+            raise ValueError(f"out_offsets must be contiguous 8-byte integers on {d}")
+        if m is not None and int(m) != out_offsets.numel():
+            raise ValueError("m is the number of out_offsets")
+        m = out_offsets.numel()
+    if not 0 <= m <= RX_ECHO_MAX:
+        raise ValueError(f"m is at most {RX_ECHO_MAX} (a descriptor's dst is 16 bits)")
+    if not 0 <= int(out_slot_bytes) <= 0xFFFF:
+        raise ValueError("out_slot_bytes is at most 65535")
+    if ip_ids is not None:
+        _byte_array("ip_ids", ip_ids, m, d, 2)
+    if check and m and not in_place:
+        oo = out_offsets.view(torch.int64)
+        if bool((oo < 0).any()) or int(oo.max()) + int(out_slot_bytes) > _nbytes(out_base):
+            raise ValueError("a slot [off, off + out_slot_bytes) runs past out_base")
+        ob, oe = out_base.data_ptr(), out_base.data_ptr() + _nbytes(out_base)
+        if ob < base.data_ptr() + _nbytes(base) and base.data_ptr() < oe:
+            raise ValueError("out_base overlaps base: the slots must not overlap the RX buffer")
+    o = _echo_out(out, m, in_place, d)
+
+    def ptr(t, some=True):
+        return (t.data_ptr() or None) if t is not None and some else None
+    c_out = _EchoOut(ptr(o.descs), ptr(o.dsts), ptr(o.af), ptr(o.status), ptr(o.src),
+                     ptr(o.tx_off, m), ptr(o.count), ptr(o.skipped))
+    rx = n != 0 and ns != 0
+    with _on_device(d):
+        _check("wc_rx_echo", _lib.active().wc_rx_echo(
+            ptr(base, rx), ptr(offsets, rx), ptr(frame_lens, rx), n, ptr(records, rx),
+            ptr(lst, rx), ptr(start, rx), ptr(echo_map, rx), ns, ptr(ip_ids, m),
+            ptr(out_base, m), ptr(out_offsets, m), int(out_slot_bytes), m, ctypes.byref(c_out),
+            _stream_ptr(stream, d)))
+    return o
+
+
+# --------------------------------------------------------------------------
 # TX seal (what mk_ip4_hdr and udp_tx store, computed and stored on the device).
 
 # enum wc_tx_status (include/warpcore_gpu/wc_cksum.h)

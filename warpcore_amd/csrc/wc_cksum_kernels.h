@@ -419,6 +419,38 @@ struct RxAnswerArgs {
 hipError_t launch_rx_answer_frames(const RxAnswerArgs &a, int cus, hipStream_t st);
 hipError_t launch_rx_answer_apply(const RxAnswerArgs &a, hipStream_t st);
 
+// RX echo (wc_k_rxecho.hip; the map and the copy in wc_rx_echo.h): the
+// delivered frames of the switched-on sockets as a TX batch -- all m entries
+// of desc / dsts / af / status (and src / tx_off where given), *count, the
+// payloads in copy mode (out_base / out_off given, tx_off NULL) -- from one
+// launch of re::grid_of(m) one-wave workgroups for any n <= 2^32 and m <=
+// re::kMax.  n = 0 or ns = 0: no RX pointer is looked at.
+struct RxEchoArgs {
+    const uint8_t *base;
+    const uint64_t *offs;
+    const uint16_t *flens;
+    uint64_t n;
+    const void *rec;
+    const uint32_t *list;
+    const uint64_t *start;
+    const uint16_t *map;
+    uint32_t ns;
+    const uint16_t *ip_id;
+    uint8_t *out_base;
+    const uint64_t *out_off;
+    uint32_t out_slot_bytes;
+    uint32_t m;
+    uint32_t *desc;
+    uint32_t *dsts;
+    uint8_t *af;
+    uint8_t *status;
+    uint32_t *src;
+    uint64_t *tx_off;
+    uint64_t *count;
+    uint64_t *skipped;
+};
+hipError_t launch_rx_echo(const RxEchoArgs &a, hipStream_t st);
+
 // Resident small-batch server (wc_k_serve.hip).  Host-mapped pinned memory:
 // one record per packet, written by the host (seq last), polled / read by the
 // server's waves; one result slot per packet, written by the GPU in one
